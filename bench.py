@@ -1,7 +1,24 @@
 """KD training-step throughput on MI355X (BASELINE.json metric), one JSON line on rank 0.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--config c1|c2|c3|c4] [--no-cpu-baseline] [--cpu-extrapolate]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--config c1|c2|c3|c4] [--dump-outputs DIR]
+    python bench.py --full [...] [--no-cpu-baseline] [--cpu-extrapolate] [--no-timer] [--no-delta] [--no-teacher-rate]
     python -m torch.distributed.run --nproc-per-node N --master-addr 127.0.0.1 ... bench.py --gpus N
+
+A plain run does only what the headline figure needs: it builds the models, warms up, times
+the K steps, writes the last timed step's outputs when `--dump-outputs DIR` is given and
+prints the line (metric, value, unit, ms_per_step, ...; the legs below are null in it).
+`--full` adds, after the timed region, every other leg: the idle-GPU host enqueue step, the
+serialized roofline pass (per-GEMM HIP events), the teacher-forward rate, c4's fp8 teacher
+delta, kd_loss_delta (the CPU oracle on a step's logits), the CPU baseline and, for N > 1,
+the gradient all-reduce timed alone; the `--no-*` switches drop single legs of it.
+
+`--dump-outputs DIR` writes what a caller of the timed path holds after the last timed step
+as float32 DIR/<name>.npy (rank 0): `loss` (training_step's return value), `loss_terms`
+(KD term, student CE, teacher CE, total) and, at DUMP_SAMPLE fixed seeded positions of the
+student's flat parameter buffer, `student_weights_sample` (the fp32 master weights after the
+last AdamW step) and `student_exp_avg_sample` (AdamW's first moment, i.e. the gradients).
+The inputs and initial weights are seeded, so two builds run with the same arguments see
+identical inputs and their dumps compare output for output.
 
 `--gpus N` with N > 1 outside a torch.distributed launcher starts the N ranks itself (one
 process per GPU, `torch.distributed.run` as a child process, before this process touches the
@@ -361,6 +378,31 @@ def fp8_teacher_delta(m, batch):
     return f
 
 
+DUMP_SAMPLE = 1 << 20   # positions of the student's flat parameter buffer written by --dump-outputs (2 x 4 MB)
+
+
+def capture_outputs(m, loss):
+    """--dump-outputs: what a caller of the timed path holds after its last step, as float32 host
+    arrays.  Called right after the timed region (every stream synchronized), before any other leg
+    takes a step.  The sample positions are fixed: a CPU generator with a constant seed."""
+    import torch
+    P = m.student_model.P
+    idx = torch.randint(0, P.numel, (min(DUMP_SAMPLE, P.numel),),
+                        generator=torch.Generator().manual_seed(20240607)).sort().values.to(P.master.device)
+    out = {"loss": loss.detach().reshape(1), "loss_terms": m.last_terms,
+           "student_weights_sample": P.master[idx], "student_exp_avg_sample": P.exp_avg[idx]}
+    torch.cuda.synchronize()
+    return {k: v.float().cpu().numpy() for k, v in out.items()}
+
+
+def write_outputs(arrays, path):
+    import numpy as np
+    d = Path(path)
+    d.mkdir(parents=True, exist_ok=True)
+    for k, v in arrays.items():
+        np.save(d / f"{k}.npy", v)
+
+
 def _free_port() -> int:
     import socket
     with socket.socket() as so:
@@ -507,6 +549,13 @@ def main():
     ap.add_argument("--image", default="336x336",
                     help="image size HxW of the synthetic batch: 336x336 (BASELINE's, L 1536, 2 tiles) or a SUNRGBD "
                          "size, e.g. 480x640 (anyres 5 tiles, 2,929 image tokens, L 2,980; DS:185-212)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed region also run every other leg: idle-GPU host enqueue step, roofline "
+                         "pass, teacher-forward rate, fp8 teacher delta (c4), kd_loss_delta, CPU baseline, the "
+                         "all-reduce timed alone (N > 1); default: the timed steps and the result line only")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="write the last timed step's outputs (loss, loss terms, a fixed seeded sample of the "
+                         "updated student weights and of AdamW's first moment) as float32 DIR/<name>.npy")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--cpu-extrapolate", action="store_true",
                     help="cpu_baseline: depth-1/3 runs extrapolated by per-layer FLOP share instead of the "
@@ -525,6 +574,8 @@ def main():
                     help="skip the teacher-forward rate pass (profiling runs: its launches would enter the "
                          "roofline kernel's rocprof average)")
     a = ap.parse_args()
+    if a.shapes and not a.full:
+        ap.error("--shapes is written from the roofline pass: it needs --full")
 
     env_world = os.environ.get("WORLD_SIZE")
     if env_world is None and (a.gpus or 1) > 1:
@@ -602,20 +653,24 @@ def main():
         dist.all_gather(g, torch.tensor([dt], dtype=torch.float64, device=dev))
         per_rank = [float(v.item()) for v in g]
         dt = max(per_rank)
-    comm = allreduce_cost(m, dist, dev, world) if world > 1 else None
+    if a.dump_outputs and rank == 0:   # the last timed step's outputs, before any other leg takes a step
+        write_outputs(capture_outputs(m, loss), a.dump_outputs)
+    comm = allreduce_cost(m, dist, dev, world) if (a.full and world > 1) else None
     loss_v = float(loss.item())
-    # host cost of enqueueing ONE step onto an idle GPU (in the timed loop the HIP queue is
-    # full and every launch waits for a slot, so host_enqueue tracks the GPU time)
-    torch.cuda.synchronize()
-    th = time.perf_counter()
-    step(a.warmup + a.steps + 5)
-    host_idle_ms = (time.perf_counter() - th) * 1e3
-    torch.cuda.synchronize()
+    host_idle_ms = None
+    if a.full:
+        # host cost of enqueueing ONE step onto an idle GPU (in the timed loop the HIP queue is
+        # full and every launch waits for a slot, so host_enqueue tracks the GPU time)
+        torch.cuda.synchronize()
+        th = time.perf_counter()
+        step(a.warmup + a.steps + 5)
+        host_idle_ms = (time.perf_counter() - th) * 1e3
+        torch.cuda.synchronize()
     # ---- after the timed region: roofline pass (two fully serialized steps: the student
     # forward behind the teacher forward, the weight gradients on the main stream; every GEMM
     # bracketed by HIP events on its launch stream, so a kernel's duration is its own and not
     # shared with a concurrent stream)
-    if not a.no_timer:
+    if a.full and not a.no_timer:
         m.concurrent_student = False
         m.student_model.wlane.serial = True   # the backward's weight gradients on the main stream too
         ops.TIMER.reset()
@@ -692,7 +747,8 @@ def main():
                     measured="HIP events on the launch stream over 2 serialized steps after the timed region",
                     bf16_student_swiglu=None if not fwd else dict(avg_launch_us=round(fwd["avg_ms"] * 1e3, 2),
                                                                   tflops=round(fwd["flops"] / (fwd["total_ms"] * 1e-3) / 1e12, 1)))
-    tfwd = teacher_forward_rate(m, batches[0]) if (m.teacher_model is not None and not a.no_teacher_rate) else None
+    tfwd = teacher_forward_rate(m, batches[0]) if (a.full and m.teacher_model is not None
+                                                   and not a.no_teacher_rate) else None
     out = {
         "metric": f"KD samples/sec/step (7B->0.5B, {a.image})",
         "value": round(value, 4),
@@ -717,7 +773,7 @@ def main():
         "per_rank_ms_per_step": [round(v / a.steps * 1e3, 2) for v in per_rank],
         "grad_allreduce": comm,
         "host_enqueue_ms_per_step": round(host_dt * 1e3 / a.steps, 2),
-        "host_enqueue_ms_idle_step": round(host_idle_ms, 2),
+        "host_enqueue_ms_idle_step": None if host_idle_ms is None else round(host_idle_ms, 2),
         "tflop_per_sample": round(tf_sample, 2),
         "loss": round(loss_v, 5),
         "teacher_fwd": tfwd,
@@ -728,9 +784,9 @@ def main():
     }
     if teacher_fp8:
         out["dtype"] = f"bf16 (student, loss) + fp8 e4m3 teacher linears ({m.teacher_fp8})"
-        if rank == 0:
+        if a.full and rank == 0:
             out["fp8_teacher_delta"] = fp8_teacher_delta(m, batches[0])
-    if not a.no_delta:
+    if a.full and not a.no_delta:
         # one more step with its logits kept: the fused loss kernel's terms vs the CPU oracle
         # on the same (bf16) logits.  Every rank takes the step (its backward all-reduces);
         # rank 0 compares.
@@ -744,7 +800,7 @@ def main():
                 out["kd_loss_delta"] = kd_loss_delta(m, batches[(a.warmup + a.steps + 2) % 2], (variant, T))
             except Exception as e:  # report, never hide
                 out["kd_loss_delta"] = {"error": repr(e)}
-    if rank == 0 and world == 1 and not a.no_cpu_baseline:
+    if a.full and rank == 0 and world == 1 and not a.no_cpu_baseline:
         threads = host_cpu_info()[0]
         _progress(f"timed region done ({value:.3f} samples/s); cpu_baseline on {threads} threads")
         try:

@@ -45,6 +45,27 @@ def test_single_rank_default():
     assert _json_line(r.stdout)["n_gpus"] == 1
 
 
+def test_full_and_dump_outputs_are_options():
+    """--full and --dump-outputs parse (the dry run has no model: nothing is written); --shapes comes
+    from the roofline pass, so without --full it is an error, not an empty file."""
+    r = _run(["--dry", "--full", "--dump-outputs", "unused", "--steps", "1", "--warmup", "0"])
+    assert r.returncode == 0, r.stderr[-2000:]
+    assert _json_line(r.stdout)["steps"] == 1
+    r = _run(["--dry", "--shapes", "unused.json", "--steps", "1"])
+    assert r.returncode != 0 and "--full" in r.stderr
+
+
+def test_write_outputs_float32_npy(tmp_path):
+    import numpy as np
+    sys.path.insert(0, str(REPO))
+    import bench
+    arrays = {"loss": np.array([1.5], np.float32), "loss_terms": np.arange(4, dtype=np.float32)}
+    bench.write_outputs(arrays, tmp_path / "a" / "b")   # the directory is created
+    for k, v in arrays.items():
+        got = np.load(tmp_path / "a" / "b" / f"{k}.npy")
+        assert got.dtype == np.float32 and np.array_equal(got, v)
+
+
 def test_world_size_mismatch_is_an_error():
     r = _run(["--gpus", "2", "--dry", "--steps", "1"], env_extra={"WORLD_SIZE": "1", "RANK": "0", "LOCAL_RANK": "0"})
     assert r.returncode != 0

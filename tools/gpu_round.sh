@@ -12,15 +12,15 @@
 # kindparity every other module (DT phases 1-3, FB, BD) at full depth vs the fp32 oracle
 #            (FULL_KINDS, default "dt1 dt2 dt3 fb bd") -> full_depth_kinds.json
 # sunparity  c1 at full depth on the SUNRGBD 480x640 geometry (5 tiles, L 2980) vs the fp32 oracle -> full_depth_sunrgbd.json
-# sunbench   bench.py --image 480x640 (the c1 line at SUNRGBD geometry) -> bench_c1_sunrgbd.json
+# sunbench   bench.py --full --image 480x640 (the c1 line at SUNRGBD geometry) -> bench_c1_sunrgbd.json
 # c4parity   BASELINE c4 itself at full depth (DT phase 3 + fp8 lm_mlp teacher) vs the fp32 oracle -> c4_full_depth.json
 # hnprofile  the student's hidden-state error vs the fp32 oracle at SigLIP / Qwen2 depths -> depth_profile.json
 # fp8study   tools/fp8_c4_study.py: the c4 KD term's fp8-vs-bf16 move split into LoCa top-2 flips and smooth change,
 #            product library, then the A/B library with the GEMM k-loop stagger off -> fp8_c4*.json
 # parity     the reduced-depth fixtures' per-term / per-parameter report -> parity.json
 # ntx        tools/ntx_bias_study.py (NT-Xent-only bias gradients) -> ntx_bias.json
-# bench      bench.py (the driver's default line; BENCH_ARGS appended) -> bench.json
-# c2|c3|c4   bench.py --config cN --no-cpu-baseline -> bench_cN.json
+# bench      bench.py --full (every leg of the line; BENCH_ARGS appended) -> bench.json
+# c2|c3|c4   bench.py --full --config cN --no-cpu-baseline -> bench_cN.json
 # ab         the c1 bench once per setting in AB_SETS ("|"-separated env settings, read by the A/B
 #            library only when KDSTEP_LIB points at it; bench flags in AB_ARGS) -> ab_<i>.json
 # prof       rocprofv3 --kernel-trace --stats of a serialized bench -> prof/ (kernel_stats.csv)
@@ -56,7 +56,7 @@ for s in $STEPS; do
                 --out $O/full_depth.json > $O/full_depth.log 2>&1 || fail fullparity $O/full_depth.log ;;
     sunparity) timeout -k 10 900 python -u tools/parity_report.py --full-depth --image 480x640 \
                 --out $O/full_depth_sunrgbd.json > $O/full_depth_sunrgbd.log 2>&1 || fail sunparity $O/full_depth_sunrgbd.log ;;
-    sunbench) timeout -k 10 600 python -u bench.py --image 480x640 --no-cpu-baseline > $O/bench_c1_sunrgbd.json 2> $O/bench_sun.err || fail sunbench $O/bench_sun.err
+    sunbench) timeout -k 10 600 python -u bench.py --full --image 480x640 --no-cpu-baseline > $O/bench_c1_sunrgbd.json 2> $O/bench_sun.err || fail sunbench $O/bench_sun.err
             tail -1 $O/bench_c1_sunrgbd.json | cut -c1-240 ;;
     c4parity) timeout -k 10 900 python -u tools/parity_report.py --c4-full-depth --out $O/c4_full_depth.json \
                 > $O/c4_full_depth.log 2>&1 || fail c4parity $O/c4_full_depth.log ;;
@@ -68,9 +68,9 @@ for s in $STEPS; do
             grep "seed" $O/fp8_c4.log $O/fp8_c4_nostagger.log ;;
     parity) timeout -k 10 600 python -u tools/parity_report.py --out $O/parity.json $PARITY_KINDS > $O/parity.log 2>&1 || fail parity $O/parity.log ;;
     ntx)    timeout -k 10 300 python -u tools/ntx_bias_study.py > $O/ntx_bias.json 2> $O/ntx_bias.err || fail ntx $O/ntx_bias.err ;;
-    bench)  timeout -k 10 900 python -u bench.py $BENCH_ARGS > $O/bench.json 2> $O/bench.err || fail bench $O/bench.err
+    bench)  timeout -k 10 900 python -u bench.py --full $BENCH_ARGS > $O/bench.json 2> $O/bench.err || fail bench $O/bench.err
             tail -1 $O/bench.json | cut -c1-240 ;;
-    c2|c3|c4) timeout -k 10 600 python -u bench.py --config $s --no-cpu-baseline > $O/bench_$s.json 2> $O/bench_$s.err || fail "bench $s" $O/bench_$s.err
+    c2|c3|c4) timeout -k 10 600 python -u bench.py --full --config $s --no-cpu-baseline > $O/bench_$s.json 2> $O/bench_$s.err || fail "bench $s" $O/bench_$s.err
             tail -1 $O/bench_$s.json | cut -c1-240 ;;
     ab)     IFS='|' read -ra SETS <<< "$AB_SETS"; i=0
             for v in "${SETS[@]}"; do
@@ -78,7 +78,7 @@ for s in $STEPS; do
               env $v timeout -k 10 300 python -u bench.py --no-cpu-baseline --no-delta --no-timer $AB_ARGS > $O/ab_$i.json 2> $O/ab_$i.err || fail "ab $i" $O/ab_$i.err
               python3 -c "import json; d=json.loads(open('$O/ab_$i.json').read().strip().splitlines()[-1]); print('[$v]', d['value'], d['ms_per_step'])"
             done ;;
-    prof)   timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof -o run -- python3 bench.py --steps 5 --warmup 2 --serial --no-teacher-rate --no-cpu-baseline --no-delta $BENCH_ARGS > $O/prof.log 2>&1 || fail prof $O/prof.log 20 ;;
+    prof)   timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof -o run -- python3 bench.py --full --steps 5 --warmup 2 --serial --no-teacher-rate --no-cpu-baseline --no-delta $BENCH_ARGS > $O/prof.log 2>&1 || fail prof $O/prof.log 20 ;;
     step)   timeout -k 10 300 rocprofv3 --kernel-trace -d $O/profstep -o run -- python3 bench.py --steps 5 --warmup 2 --no-cpu-baseline --no-delta --no-timer --no-teacher-rate $BENCH_ARGS > $O/profstep.log 2>&1 || fail profstep $O/profstep.log 20
             DB=$(ls $O/profstep/*/run_results.db $O/profstep/run_results.db 2>/dev/null | head -1)
             python3 tools/step_breakdown.py $DB 40 > $O/step_breakdown.txt 2>&1
