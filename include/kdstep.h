@@ -463,6 +463,44 @@ int kd_gen_select(const void* logits, int V, int64_t* seq, int len, int32_t* cur
 int kd_rope_row(const float* cos_table, const float* sin_table, int hh, const int32_t* cur_dev, float* cos_row,
                 float* sin_row, void* stream);
 
+/* Batched greedy decode: the step above for nb <= 16 rows (prompts) at once, so a step streams
+ * the weights once for all of them.  Per-row state lives on the device: cur_dev [nb] int32, the
+ * rows' lengths (each as *cur_dev above).  All four are stream-ordered, make no host sync and take
+ * arguments that are fixed across steps (one captured graph replays the step).
+ * Batch invariance: what a row gets depends on that row's data alone -- never on nb, on the other
+ * rows or on the slot the row occupies.  Every launch plan (grid, K split, reduction order) is a
+ * function of the layer's shape only, and every reduction runs in a fixed order without
+ * floating-point atomics, so row b of a result is bit-identical to the nb = 1 call on that row.
+ * kd_gemv_batch: y [nb, N] bf16 (contiguous) = epilogue(x'[nb, K] W[N, K]^T) on the bf16 MFMA with
+ *   the batch as its M dimension; x rows ldx apart, W rows ldw >= K apart, K % 8 == 0 (any N);
+ *   fp32 accumulation, rounded to bf16 on store.  Epilogues as kd_gemv (`extra` = bias [N] for 1,
+ *   the residual [nb, N] contiguous for 2); norm_w: the Qwen2RMSNorm of each row fused in front,
+ *   rounded to bf16 as kd_norm_fwd stores it.  Shapes whose K is split across workgroups need
+ *   kd_gemv_batch_workspace_size(N, K, epilogue) bytes of workspace (0: none is read).
+ * kd_attn_decode_batch: kd_attn_decode for row b over positions [0, cur_dev[b]) of its own cache:
+ *   q [H, nb, hdp], k_new/v_new [HKV, nb, hdp] (head-major over the batch: kd_qkv_split with
+ *   B = 1, S = nb), caches [nb, HKV, smax, hdp], o [nb, H * hd]; row b's k_new/v_new are stored at
+ *   position cur_dev[b] - 1 of its cache, no other cache element is written.
+ * kd_gen_select_batch: kd_gen_select per row: logits [nb, V] (rows ld_logits apart), seq
+ *   [nb, smax] int64; writes seq[b][cur_dev[b]], out[b] (optional) and cur_dev[b] += 1.
+ *   workspace >= nb * V bytes.
+ * kd_rope_rows: cos/sin row of position cur_dev[b] - 1 of the [table_rows, hh] tables into row b
+ *   of [nb, hh] buffers: as kd_qkv_split's tables with (B = 1, S = nb) they rotate token b by its
+ *   own position. */
+size_t kd_gemv_batch_workspace_size(int N, int K, int epilogue);
+int kd_gemv_batch(const void* x, int64_t ldx, int nb, const void* W, int64_t ldw, const void* extra, void* y, int N,
+                  int K, int epilogue, int inter, const void* norm_w, float eps, void* workspace,
+                  size_t workspace_bytes, void* stream);
+size_t kd_attn_decode_batch_workspace_size(int nb, int H, int hd, int smax);
+int kd_attn_decode_batch(const void* q, const void* k_new, const void* v_new, void* k_cache, void* v_cache, void* o,
+                         int nb, int H, int HKV, int hd, int hdp, int smax, const int32_t* cur_dev, void* workspace,
+                         size_t workspace_bytes, void* stream);
+int kd_gen_select_batch(const void* logits, int64_t ld_logits, int V, int64_t* seq, int smax, int nb,
+                        int32_t* cur_dev, float repetition_penalty, int no_repeat_ngram, void* workspace,
+                        size_t workspace_bytes, int64_t* out, void* stream);
+int kd_rope_rows(const float* cos_table, const float* sin_table, int hh, int table_rows, int nb,
+                 const int32_t* cur_dev, float* cos_rows, float* sin_rows, void* stream);
+
 /* --------------------------------------------------------- model runtime ---- */
 /* One LLaVA-OneVision instance (SigLIP -> projector -> anyres pack -> Qwen2 -> lm_head)
  * whose forward and backward layer loops run in the library (SURVEY §8b "teacher forward"

@@ -179,6 +179,13 @@ SIGNATURES = {
     "kd_gemv": (_i32, [_vp, _vp, _i64, _vp, _vp, _i32, _i32, _i32, _i32, _vp, _f32, _vp]),
     "kd_gen_select": (_i32, [_vp, _i32, _vp, _i32, _vp, _f32, _i32, _vp, _sz, _vp, _vp]),
     "kd_rope_row": (_i32, [_vp, _vp, _i32, _vp, _vp, _vp, _vp]),
+    "kd_gemv_batch_workspace_size": (_sz, [_i32, _i32, _i32]),
+    "kd_gemv_batch": (_i32, [_vp, _i64, _i32, _vp, _i64, _vp, _vp, _i32, _i32, _i32, _i32, _vp, _f32, _vp, _sz, _vp]),
+    "kd_attn_decode_batch_workspace_size": (_sz, [_i32, _i32, _i32, _i32]),
+    "kd_attn_decode_batch": (_i32, [_vp, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _i32, _vp, _vp, _sz,
+                                    _vp]),
+    "kd_gen_select_batch": (_i32, [_vp, _i64, _i32, _vp, _i32, _i32, _vp, _f32, _i32, _vp, _sz, _vp, _vp]),
+    "kd_rope_rows": (_i32, [_vp, _vp, _i32, _i32, _i32, _vp, _vp, _vp, _vp]),
     "kd_image_resize_u8": (_i32, [_vp, _i32, _i32, _vp, _i32, _i32, _vp, _sz, _vp]),
     "kd_anyres_tiles": (_i32, [_vp, _vp, _i32, _i32, _i32, _i32, _i32, _i32, _vp, _vp, _i32, _vp]),
     "kd_anyres_batch_map": (_i32, [_vp, _i32, _i32, _vp, _i32, _vp]),

@@ -159,6 +159,26 @@ int kd_gen_select(const void* logits, int V, int64_t* seq, int len, int32_t* cur
 int kd_rope_row(const float* c, const float* sn, int hh, const int32_t* cur, float* cr, float* sr, void* s) {
     return kd::launch_rope_row(c, sn, hh, cur, cr, sr, s);
 }
+size_t kd_gemv_batch_workspace_size(int N, int K, int epi) { return kd::gemv_batch_ws(N, K, epi); }
+int kd_gemv_batch(const void* x, int64_t ldx, int nb, const void* W, int64_t ldw, const void* extra, void* y, int N,
+                  int K, int epi, int I, const void* norm_w, float eps, void* ws, size_t wsb, void* s) {
+    return kd::launch_gemv_batch(x, ldx, nb, W, ldw, extra, y, N, K, epi, I, norm_w, eps, ws, wsb, s);
+}
+size_t kd_attn_decode_batch_workspace_size(int nb, int H, int hd, int smax) {
+    return kd::attn_decode_batch_ws(nb, H, hd, smax);
+}
+int kd_attn_decode_batch(const void* q, const void* kn, const void* vn, void* kc, void* vc, void* o, int nb, int H,
+                         int HKV, int hd, int hdp, int smax, const int32_t* cur, void* ws, size_t wsb, void* s) {
+    return kd::launch_attn_decode_batch(q, kn, vn, kc, vc, o, nb, H, HKV, hd, hdp, smax, cur, ws, wsb, s);
+}
+int kd_gen_select_batch(const void* logits, int64_t ldl, int V, int64_t* seq, int smax, int nb, int32_t* cur,
+                        float penalty, int ngram, void* ws, size_t wsb, int64_t* out, void* s) {
+    return kd::launch_gen_select_batch(logits, ldl, V, seq, smax, nb, cur, penalty, ngram, ws, wsb, out, s);
+}
+int kd_rope_rows(const float* c, const float* sn, int hh, int rows, int nb, const int32_t* cur, float* cr, float* sr,
+                 void* s) {
+    return kd::launch_rope_rows(c, sn, hh, rows, nb, cur, cr, sr, s);
+}
 size_t kd_image_resize_workspace_size(int H, int W, int oh, int ow) { return kd::image_resize_ws(H, W, oh, ow); }
 int kd_image_resize_u8(const uint8_t* in, int H, int W, uint8_t* out, int oh, int ow, void* ws, size_t ws_bytes,
                        void* s) {

@@ -12,7 +12,12 @@
 //                   (bans every token that would repeat an n-gram of the sequence), then the
 //                   greedy argmax (lowest index on ties, as torch.argmax), appended to the
 //                   device-resident sequence (no host sync per token).
+// and their batched forms for generate_batch() (up to 16 prompts per step, per-row lengths on the
+// device, batch-invariant): k_gemv_batch (bf16 MFMA, the batch as M), k_attn_decode_part_batch,
+// k_gen_select_batch, k_rope_rows.
 #include "common.h"
+
+#include <algorithm>
 
 namespace kd {
 
@@ -300,7 +305,487 @@ __global__ void k_rope_row(const float* __restrict__ cos_t, const float* __restr
     }
 }
 
+// ------------------------------------------------------------ batched decode (nb <= 16 rows) ----
+// Every per-row quantity below is computed by code whose arithmetic and order depend on the row's
+// own data only: never on nb, nor on the slot the row occupies (batch invariance, include/kdstep.h).
+
+// Split-KV decode attention of row b = blockIdx.z with the row's own length cur_dev[b], cache
+// [HKV, smax, hdp] and partial block: k_attn_decode_part's split, but one workgroup serves up to
+// AB_R query heads of a KV head (blockIdx.x = kv head x head group), so the chunk's K and V tiles
+// are read once for the GQA group instead of once per query head (at nb = 16 the per-head form
+// spent more of the step here than in the linears).  q / k_new / v_new are head-major over the
+// batch ([H | HKV, nb, hdp]: what kd_qkv_split(B = 1, S = nb) writes).  The partials are laid out
+// [nb * H, nch, HD + 2], so k_attn_decode_combine merges them on a grid of nb * H.
+constexpr int AB_R = 8;
+template <int HD>
+__global__ void __launch_bounds__(NT) k_attn_decode_part_batch(const bf16* __restrict__ q, const bf16* __restrict__ k_new,
+                                                               const bf16* __restrict__ v_new, bf16* __restrict__ kc,
+                                                               bf16* __restrict__ vc, float* __restrict__ part, int H,
+                                                               int HKV, int hdp, int smax, int nb,
+                                                               const int* __restrict__ cur_dev, float scale) {
+    __shared__ __attribute__((aligned(16))) float q_s[AB_R][HD];
+    __shared__ float p_s[AB_R][CH];
+    __shared__ float m_s[AB_R], l_s[AB_R];
+    __shared__ float acc_s[AB_R][NT];
+    const int R = H / HKV, ng = (R + AB_R - 1) / AB_R;
+    const int kvh = blockIdx.x / ng, g8 = blockIdx.x - kvh * ng, c = blockIdx.y, b = blockIdx.z, nch = gridDim.y;
+    const int h0 = kvh * R + g8 * AB_R, Rg = min(AB_R, R - g8 * AB_R);   // query heads [h0, h0 + Rg)
+    const int n = cur_dev[b], j0 = c * CH;
+    const size_t hstride = (size_t)nch * (HD + 2);
+    float* pp = part + (((size_t)b * H + h0) * nch + c) * (HD + 2);   // head h0 + r: + r * hstride
+    if (j0 >= n || n > smax) {   // empty chunk; a length outside [1, smax] touches no cache row
+        for (int i = threadIdx.x; i < Rg * (HD + 2); i += NT) {
+            const int r = i / (HD + 2), e = i - r * (HD + 2);
+            pp[r * hstride + e] = e == 0 ? -INFINITY : 0.f;
+        }
+        return;
+    }
+    bf16* K = kc + ((size_t)b * HKV + kvh) * smax * hdp;
+    bf16* V = vc + ((size_t)b * HKV + kvh) * smax * hdp;
+    const bf16* kn = k_new + ((size_t)kvh * nb + b) * hdp;
+    const bf16* vn = v_new + ((size_t)kvh * nb + b) * hdp;
+    if (c == 0 && g8 == 0)
+        for (int d = threadIdx.x; d < hdp; d += NT) {
+            K[(size_t)(n - 1) * hdp + d] = kn[d];
+            V[(size_t)(n - 1) * hdp + d] = vn[d];
+        }
+    // this thread's share of the V tile, issued before the scores: dim d of keys g, g + G, ...
+    constexpr int G = NT / HD, NV = CH / G;
+    const int d = threadIdx.x % HD, g = threadIdx.x / HD;
+    const int jend = min(CH, n - j0);
+    float vr[NV];
+#pragma unroll
+    for (int i = 0; i < NV; ++i) {
+        // every load unconditional (keys past the chunk's end re-read the row's own v_new): a load
+        // under a lane-dependent branch waits for its own round trip, NV of them in a row
+        const int jj = g + i * G, j = min(j0 + jj, n - 1);
+        const bf16* src = j == n - 1 ? vn + d : V + (size_t)j * hdp + d;
+        const float v = (float)*src;
+        vr[i] = jj < jend ? v : 0.f;
+    }
+    for (int i = threadIdx.x; i < AB_R * HD; i += NT) {   // heads past Rg: zeros (computed, never stored)
+        const int r = i / HD, dd = i - r * HD;
+        q_s[r][dd] = r < Rg ? (float)q[((size_t)(h0 + r) * nb + b) * hdp + dd] : 0.f;
+    }
+    __syncthreads();
+    // scores: key j0 + threadIdx/4, lane quarter (threadIdx & 3) covers HD/4 dims of every head
+    constexpr int DQ = HD / 4;
+    const int kj = j0 + (threadIdx.x >> 2), qd = (threadIdx.x & 3) * DQ;
+    float a[AB_R];
+#pragma unroll
+    for (int r = 0; r < AB_R; ++r) a[r] = 0.f;
+    {
+        const int kjc = min(kj, n - 1);   // keys past n: the own row again, masked below
+        const bf16* kr = (kjc == n - 1 ? kn : K + (size_t)kjc * hdp) + qd;
+#pragma unroll
+        for (int dd = 0; dd < DQ; dd += 8) {
+            const bf16x8 k8 = *(const bf16x8*)(kr + dd);
+#pragma unroll
+            for (int r = 0; r < AB_R; ++r) {
+                const f32x4 qa = *(const f32x4*)&q_s[r][qd + dd], qb = *(const f32x4*)&q_s[r][qd + dd + 4];
+#pragma unroll
+                for (int e = 0; e < 4; ++e) a[r] += qa[e] * (float)k8[e];
+#pragma unroll
+                for (int e = 0; e < 4; ++e) a[r] += qb[e] * (float)k8[4 + e];
+            }
+        }
+    }
+#pragma unroll
+    for (int r = 0; r < AB_R; ++r) {
+        a[r] += __shfl_xor(a[r], 1, 64);
+        a[r] += __shfl_xor(a[r], 2, 64);
+        if ((threadIdx.x & 3) == 0) p_s[r][threadIdx.x >> 2] = kj < n ? a[r] * scale : -INFINITY;
+    }
+    __syncthreads();
+    // softmax of the chunk, one wave per head (lane = key): wave w takes heads w, w + 4
+    const int w = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    for (int r = w; r < AB_R; r += NT / 64) {
+        const float s = p_s[r][lane];
+        const float m = wave_max(s);   // key j0 is valid, so m is finite
+        const float pv = j0 + lane < n ? __expf(s - m) : 0.f;
+        const float l = wave_sum(pv);
+        p_s[r][lane] = pv;
+        if (lane == 0) { m_s[r] = m; l_s[r] = l; }
+    }
+    __syncthreads();
+    float acc[AB_R];
+#pragma unroll
+    for (int r = 0; r < AB_R; ++r) acc[r] = 0.f;
+#pragma unroll
+    for (int i = 0; i < NV; ++i) {
+        const int jj = g + i * G;
+#pragma unroll
+        for (int r = 0; r < AB_R; ++r) acc[r] += p_s[r][jj] * vr[i];
+    }
+#pragma unroll
+    for (int r = 0; r < AB_R; ++r) acc_s[r][threadIdx.x] = acc[r];
+    __syncthreads();
+    for (int i = threadIdx.x; i < Rg * HD; i += NT) {
+        const int r = i / HD, dd = i - r * HD;
+        float tsum = 0.f;
+#pragma unroll
+        for (int k = 0; k < G; ++k) tsum += acc_s[r][k * HD + dd];
+        pp[r * hstride + 2 + dd] = tsum;
+        if (dd == 0) { pp[r * hstride] = m_s[r]; pp[r * hstride + 1] = l_s[r]; }
+    }
+}
+
+// Skinny linear layer y[nb, N] = epilogue(x[nb, K] W[N, K]^T), nb <= 16, on
+// v_mfma_f32_16x16x32_bf16 with the batch as the M dimension: the A fragment of lane l is 8 k of
+// batch row l & 15 (rows >= nb are zero and never stored), the B fragment 8 contiguous k of weight
+// row n0 + (l & 15): one 16-B global load per lane straight from the row-major weight, every
+// weight element read once per launch, no LDS round trip.  D[row m] depends on A[row m] only, so a
+// batch row's result does not depend on its neighbours.
+// Workgroup (blockIdx.x, blockIdx.y = K slice): the slice of x ([16, slice] bf16, the RMSNorm
+// applied when norm_w is given, rounded to bf16 as stage_x rounds) is staged in LDS once;
+//   wave_n = 0  one 16-row weight tile per workgroup, its 4 waves interleave the slice's 32-k
+//               steps and their accumulators are summed through LDS in wave order;
+//   wave_n = 1  one tile per wave (the lm_head: enough tiles to fill the chip on their own).
+// With ksplit > 1 the fp32 slice sums go to `part` [ksplit, NACC, 16, N] and
+// k_gemv_batch_reduce adds them in slice order and applies the epilogue (no atomics).
+constexpr int GB_ROWS = 16;         // the MFMA's M
+constexpr int GB_MAX_STEPS = 48;    // 32-k steps per K slice: 16 x (1536 + 8) bf16 = 48.25 KiB of LDS
+constexpr int GB_PAD = 8;           // bf16 per LDS row: rows 16 B apart in the banks
+constexpr int GB_PF = 8;            // weight fragments per wave loaded ahead of the x staging
+
+template <int EPI>
+__global__ void __launch_bounds__(NT) k_gemv_batch(const bf16* __restrict__ x, int64_t ldx, const bf16* __restrict__ W,
+                                                   int64_t ldw, const bf16* __restrict__ extra, bf16* __restrict__ y,
+                                                   float* __restrict__ part, int nb, int N, int K, int I,
+                                                   const bf16* __restrict__ norm_w, float eps, int wave_n,
+                                                   int slice_steps, int ksplit) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char gb_smem[];
+    constexpr int NACC = EPI == 3 ? 2 : 1;
+    __shared__ float rstd_s[GB_ROWS];
+    __shared__ f32x4 red_s[NACC][NT / 64][64];
+    bf16* xs = (bf16*)gb_smem;
+    const int w = threadIdx.x >> 6, lane = threadIdx.x & 63, ks = blockIdx.y;
+    const int ksteps = (K + 31) >> 5;
+    const int s_beg = ks * slice_steps, s_end = min(ksteps, s_beg + slice_steps);
+    const int kb = s_beg * 32, XLD = slice_steps * 32 + GB_PAD;
+    const bf16x8 zero8 = {};
+    const int tile = wave_n ? blockIdx.x * (NT / 64) + w : blockIdx.x;
+    const int col = lane & 15, kq = (lane >> 4) * 8;
+    const int n = tile * 16 + col, nc = min(n, N - 1);   // rows past N: a valid row is read, nothing stored
+    const bf16* r0 = W + (size_t)nc * ldw;
+    const bf16* r1 = W + (size_t)(I + nc) * ldw;
+    const int s_first = s_beg + (wave_n ? 0 : w), sst = wave_n ? 1 : NT / 64;
+    // the weights do not wait for x: the wave's first GB_PF fragments are in flight while the norm
+    // and the staging of x run (a K = 896 layer's whole share); loads past the share or the K tail
+    // stay unconditional, on the row's first chunk, and are replaced by zeros
+    bf16x8 pf0[GB_PF], pf1[EPI == 3 ? GB_PF : 1];
+#pragma unroll
+    for (int i = 0; i < GB_PF; ++i) {
+        const int k = (s_first + i * sst) * 32 + kq;
+        const bool in = s_first + i * sst < s_end && k < K;
+        pf0[i] = *(const bf16x8*)(r0 + (in ? k : 0));
+        if constexpr (EPI == 3) pf1[i] = *(const bf16x8*)(r1 + (in ? k : 0));
+    }
+    if (norm_w) {   // per-row 1/rms over the whole row: 16 lanes per row, the same order in every slot
+        const int b = threadIdx.x >> 4, sub = threadIdx.x & 15;
+        float ss = 0.f;
+        if (b < nb) {
+            const bf16* xr = x + (size_t)b * ldx;
+#pragma unroll 8
+            for (int k = sub * 8; k < K; k += 128) {
+                const bf16x8 v = *(const bf16x8*)(xr + k);
+#pragma unroll
+                for (int e = 0; e < 8; ++e) ss += (float)v[e] * (float)v[e];
+            }
+        }
+#pragma unroll
+        for (int o = 8; o > 0; o >>= 1) ss += __shfl_xor(ss, o, 64);
+        if (sub == 0) rstd_s[b] = rsqrtf(ss / K + eps);
+        __syncthreads();
+    }
+    const int cpr = slice_steps * 4;   // 16-B chunks per staged row
+#pragma unroll 4
+    for (int idx = threadIdx.x; idx < GB_ROWS * cpr; idx += NT) {
+        const int b = idx / cpr, c = idx - b * cpr, k = kb + c * 8;
+        const bool in = b < nb && k < K;   // else zeros: rows >= nb and the K tail
+        const int bc = min(b, nb - 1), kc8 = min(k, K - 8);   // the loads stay unconditional, inside x
+        bf16x8 v = *(const bf16x8*)(x + (size_t)bc * ldx + kc8);
+        if (norm_w) {
+            const bf16x8 nw = *(const bf16x8*)(norm_w + kc8);
+            const float rstd = rstd_s[bc];
+#pragma unroll
+            for (int e = 0; e < 8; ++e) v[e] = (bf16)((float)v[e] * rstd * (float)nw[e]);
+        }
+        *(bf16x8*)(xs + b * XLD + c * 8) = in ? v : zero8;
+    }
+    __syncthreads();
+    const bf16* xr = xs + col * XLD + kq - kb;
+    f32x4 acc0 = {0.f, 0.f, 0.f, 0.f}, acc1 = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+    for (int i = 0; i < GB_PF; ++i) {
+        const int s = s_first + i * sst;
+        if (s < s_end) {   // wave-uniform
+            const bool in = s * 32 + kq < K;
+            const bf16x8 a = *(const bf16x8*)(xr + s * 32);
+            acc0 = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, in ? pf0[i] : zero8, acc0, 0, 0, 0);
+            if constexpr (EPI == 3) acc1 = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, in ? pf1[i] : zero8, acc1, 0, 0, 0);
+        }
+    }
+#pragma unroll 4
+    for (int s = s_first + GB_PF * sst; s < s_end; s += sst) {
+        const int k = s * 32 + kq;
+        const bool in = k < K;   // K tail (K % 32 != 0): the load stays unconditional, on the row's first chunk
+        const bf16x8 a = *(const bf16x8*)(xr + s * 32);
+        const bf16x8 l0 = *(const bf16x8*)(r0 + (in ? k : 0));
+        acc0 = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, in ? l0 : zero8, acc0, 0, 0, 0);
+        if constexpr (EPI == 3) {
+            const bf16x8 l1 = *(const bf16x8*)(r1 + (in ? k : 0));
+            acc1 = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, in ? l1 : zero8, acc1, 0, 0, 0);
+        }
+    }
+    if (!wave_n) {   // the 4 waves' K shares, summed in wave order
+        red_s[0][w][lane] = acc0;
+        if constexpr (EPI == 3) red_s[1][w][lane] = acc1;
+        __syncthreads();
+        if (w != 0) return;
+        acc0 = ((red_s[0][0][lane] + red_s[0][1][lane]) + red_s[0][2][lane]) + red_s[0][3][lane];
+        if constexpr (EPI == 3) acc1 = ((red_s[1][0][lane] + red_s[1][1][lane]) + red_s[1][2][lane]) + red_s[1][3][lane];
+    }
+    if (n >= N) return;
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {   // D: column n = lane & 15, batch row (lane >> 4) * 4 + r
+        const int b = (lane >> 4) * 4 + r;
+        if (b >= nb) continue;
+        if (ksplit == 1) {
+            float v = acc0[r];
+            if constexpr (EPI == 1) v += (float)extra[n];
+            if constexpr (EPI == 2) v += (float)extra[(size_t)b * N + n];
+            if constexpr (EPI == 3) v = silu_fast(acc0[r]) * acc1[r];
+            y[(size_t)b * N + n] = (bf16)v;
+        } else {
+            part[(((size_t)ks * NACC) * GB_ROWS + b) * N + n] = acc0[r];
+            if constexpr (EPI == 3) part[(((size_t)ks * NACC + 1) * GB_ROWS + b) * N + n] = acc1[r];
+        }
+    }
+}
+
+// Sum of the K slices of k_gemv_batch in slice order, then the epilogue.  Grid (ceil(N / 256), 16):
+// fixed by N, rows >= nb exit.
+template <int EPI>
+__global__ void __launch_bounds__(NT) k_gemv_batch_reduce(const float* __restrict__ part, const bf16* __restrict__ extra,
+                                                          bf16* __restrict__ y, int nb, int N, int ksplit) {
+    constexpr int NACC = EPI == 3 ? 2 : 1;
+    const int b = blockIdx.y, n = blockIdx.x * NT + threadIdx.x;
+    if (b >= nb || n >= N) return;
+    float a0 = 0.f, a1 = 0.f;
+    for (int ks = 0; ks < ksplit; ++ks) {
+        a0 += part[(((size_t)ks * NACC) * GB_ROWS + b) * N + n];
+        if constexpr (EPI == 3) a1 += part[(((size_t)ks * NACC + 1) * GB_ROWS + b) * N + n];
+    }
+    float v = a0;
+    if constexpr (EPI == 1) v += (float)extra[n];
+    if constexpr (EPI == 2) v += (float)extra[(size_t)b * N + n];
+    if constexpr (EPI == 3) v = silu_fast(a0) * a1;
+    y[(size_t)b * N + n] = (bf16)v;
+}
+
+// k_gen_select for row b = blockIdx.x: its own logits row, sequence (row stride smax), length
+// cur_dev[b] and V bytes of flags; the arithmetic is k_gen_select's.
+__global__ void __launch_bounds__(1024) k_gen_select_batch(const bf16* __restrict__ logits_all, int64_t ldl, int V,
+                                                           int64_t* __restrict__ seq_all, int smax,
+                                                           int* __restrict__ cur_dev, float penalty, int ngram,
+                                                           uint8_t* __restrict__ flags_all, int64_t* __restrict__ out) {
+    __shared__ float sv[16];
+    __shared__ int si[16];
+    const int b = blockIdx.x;
+    const bf16* logits = logits_all + (size_t)b * ldl;
+    int64_t* seq = seq_all + (size_t)b * smax;
+    uint8_t* flags = flags_all + (size_t)b * V;
+    const int len = max(0, min(cur_dev[b], smax));   // the ids read never leave the row
+    {
+        const int v16 = ((uintptr_t)flags & 15) == 0 ? V >> 4 : 0;
+        for (int i = threadIdx.x; i < v16; i += blockDim.x) ((u32x4*)flags)[i] = u32x4{0u, 0u, 0u, 0u};
+        for (int i = (v16 << 4) + threadIdx.x; i < V; i += blockDim.x) flags[i] = 0;
+    }
+    __syncthreads();
+    if (penalty != 1.0f)
+        for (int i = threadIdx.x; i < len; i += blockDim.x) {
+            const int64_t t = seq[i];
+            if (t >= 0 && t < V) flags[t] |= 1;
+        }
+    __syncthreads();   // the two processors OR different bits into the same bytes
+    if (ngram > 0 && len + 1 >= ngram)
+        for (int i = threadIdx.x; i + ngram <= len; i += blockDim.x) {
+            bool match = true;
+            for (int k = 0; k < ngram - 1; ++k) match &= seq[i + k] == seq[len - ngram + 1 + k];
+            if (match) {
+                const int64_t t = seq[i + ngram - 1];
+                if (t >= 0 && t < V) flags[t] |= 2;
+            }
+        }
+    __syncthreads();
+    float best = -INFINITY;
+    int bi = 0x7fffffff;
+    auto consider = [&](int i, float s, uint32_t f) {
+        if (f & 1) s = s < 0.f ? __fmul_rn(s, penalty) : __fdiv_rn(s, penalty);
+        if (f & 2) s = -INFINITY;
+        if (s > best || (s == best && i < bi)) { best = s; bi = i; }   // NaN never wins
+    };
+    const int v8 = (((uintptr_t)logits & 15) == 0 && ((uintptr_t)flags & 7) == 0) ? V >> 3 : 0;
+    for (int c = threadIdx.x; c < v8; c += blockDim.x) {
+        const bf16x8 lv = ((const bf16x8*)logits)[c];
+        const u32x2 fv = ((const u32x2*)flags)[c];
+#pragma unroll
+        for (int e = 0; e < 8; ++e) consider(c * 8 + e, (float)lv[e], ((e < 4 ? fv.x : fv.y) >> (8 * (e & 3))) & 255u);
+    }
+    for (int i = (v8 << 3) + threadIdx.x; i < V; i += blockDim.x) consider(i, (float)logits[i], flags[i]);
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) {
+        const float ov = __shfl_xor(best, off, 64);
+        const int oi = __shfl_xor(bi, off, 64);
+        if (ov > best || (ov == best && oi < bi)) { best = ov; bi = oi; }
+    }
+    const int w = threadIdx.x >> 6;
+    if ((threadIdx.x & 63) == 0) { sv[w] = best; si[w] = bi; }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        for (int k = 1; k < (int)(blockDim.x >> 6); ++k)
+            if (sv[k] > best || (sv[k] == best && si[k] < bi)) { best = sv[k]; bi = si[k]; }
+        if (bi == 0x7fffffff) bi = 0;   // every score -inf: torch.argmax returns 0
+        if (len < smax) seq[len] = bi;
+        if (out) out[b] = bi;
+        cur_dev[b] = len + 1;
+    }
+}
+
+// cos/sin row of position cur_dev[b] - 1 (kept inside the table) into row b of [nb, hh] buffers.
+__global__ void k_rope_rows(const float* __restrict__ cos_t, const float* __restrict__ sin_t, int hh, int rows,
+                            const int* __restrict__ cur_dev, float* __restrict__ cos_rows, float* __restrict__ sin_rows) {
+    const int b = blockIdx.x, pos = min(max(cur_dev[b] - 1, 0), rows - 1);
+    for (int i = threadIdx.x; i < hh; i += blockDim.x) {
+        cos_rows[(size_t)b * hh + i] = cos_t[(size_t)pos * hh + i];
+        sin_rows[(size_t)b * hh + i] = sin_t[(size_t)pos * hh + i];
+    }
+}
+
 }  // namespace
+
+// Launch plan of k_gemv_batch: a function of (N, K) alone.  Never of nb.
+struct GemvBatchPlan {
+    int wg_n, wave_n, ksplit, slice_steps;
+};
+static GemvBatchPlan gemv_batch_plan(int N, int K) {
+    const int tiles = (N + 15) / 16, ksteps = (K + 31) / 32;
+    GemvBatchPlan p;
+    p.wave_n = tiles >= 2048 ? 1 : 0;
+    p.wg_n = p.wave_n ? (tiles + 3) / 4 : tiles;
+    // K slices: about one workgroup per CU (256) while every wave keeps >= 2 steps; LDS bounds the slice
+    int want = p.wave_n ? 1 : std::max(1, std::min((256 + p.wg_n - 1) / p.wg_n, ksteps / 8));
+    want = std::max(want, (ksteps + GB_MAX_STEPS - 1) / GB_MAX_STEPS);
+    p.slice_steps = (ksteps + want - 1) / want;
+    p.ksplit = (ksteps + p.slice_steps - 1) / p.slice_steps;
+    return p;
+}
+
+size_t gemv_batch_ws(int N, int K, int epi) {
+    if (N <= 0 || K <= 0) return 0;
+    const GemvBatchPlan p = gemv_batch_plan(N, K);
+    return p.ksplit == 1 ? 0 : (size_t)p.ksplit * (epi == 3 ? 2 : 1) * GB_ROWS * N * sizeof(float);
+}
+
+int launch_gemv_batch(const void* x, int64_t ldx, int nb, const void* W, int64_t ldw, const void* extra, void* y, int N,
+                      int K, int epi, int I, const void* norm_w, float eps, void* ws, size_t ws_bytes, void* stream) {
+    KD_CHECK_ARG(x && W && y, "gemv_batch: null pointer");
+    KD_CHECK_ARG(epi >= 0 && epi <= 3 && (epi == 0 || epi == 3 || extra), "gemv_batch: epilogue 0..3 (1, 2 need extra)");
+    KD_CHECK_SHAPE(nb >= 1 && nb <= GB_ROWS, "gemv_batch: 1 <= nb <= 16");
+    KD_CHECK_SHAPE(N > 0 && K > 0 && K % 8 == 0 && K <= 16384 && ldw >= K && ldw % 8 == 0 && ldx >= K && ldx % 8 == 0,
+                   "gemv_batch: K must be a multiple of 8 (<= 16384), ldw and ldx >= K and multiples of 8");
+    KD_CHECK_SHAPE(epi != 3 || I >= N, "gemv_batch: SwiGLU needs inter >= N");
+    KD_CHECK_ALIGN(W, 16, "gemv_batch: W misaligned");
+    KD_CHECK_ALIGN(x, 16, "gemv_batch: x misaligned");
+    KD_CHECK_ALIGN(norm_w, 16, "gemv_batch: norm_w misaligned");
+    const GemvBatchPlan p = gemv_batch_plan(N, K);
+    if (p.ksplit > 1 && (!ws || ws_bytes < gemv_batch_ws(N, K, epi)))
+        return fail(KD_ERR_WORKSPACE, "gemv_batch: workspace too small (kd_gemv_batch_workspace_size)");
+    const dim3 grid(p.wg_n, p.ksplit), rgrid((N + NT - 1) / NT, GB_ROWS);
+    const size_t lds = (size_t)GB_ROWS * (p.slice_steps * 32 + GB_PAD) * sizeof(bf16);
+    hipStream_t s = as_stream(stream);
+    const bf16 *xb = (const bf16*)x, *Wb = (const bf16*)W, *eb = (const bf16*)extra, *nw = (const bf16*)norm_w;
+#define KD_GB(E)                                                                                                       \
+    do {                                                                                                               \
+        hipLaunchKernelGGL(k_gemv_batch<E>, grid, dim3(NT), lds, s, xb, ldx, Wb, ldw, eb, (bf16*)y, (float*)ws, nb, N, \
+                           K, I, nw, eps, p.wave_n, p.slice_steps, p.ksplit);                                          \
+        if (p.ksplit > 1)                                                                                              \
+            hipLaunchKernelGGL(k_gemv_batch_reduce<E>, rgrid, dim3(NT), 0, s, (const float*)ws, eb, (bf16*)y, nb, N,   \
+                               p.ksplit);                                                                              \
+    } while (0)
+    switch (epi) {
+        case 0: KD_GB(0); break;
+        case 1: KD_GB(1); break;
+        case 2: KD_GB(2); break;
+        default: KD_GB(3);
+    }
+#undef KD_GB
+    KD_LAUNCH_CHECK("k_gemv_batch");
+    return KD_OK;
+}
+
+size_t attn_decode_ws(int H, int hd, int smax);
+
+size_t attn_decode_batch_ws(int nb, int H, int hd, int smax) {
+    return (size_t)std::max(nb, 0) * attn_decode_ws(H, hd, smax);
+}
+
+int launch_attn_decode_batch(const void* q, const void* k_new, const void* v_new, void* kc, void* vc, void* o, int nb,
+                             int H, int HKV, int hd, int hdp, int smax, const int* cur_dev, void* ws, size_t ws_bytes,
+                             void* stream) {
+    KD_CHECK_ARG(q && k_new && v_new && kc && vc && o && cur_dev && ws, "attn_decode_batch: null pointer");
+    KD_CHECK_SHAPE(nb >= 1 && nb <= GB_ROWS, "attn_decode_batch: 1 <= nb <= 16");
+    KD_CHECK_SHAPE(hd == 64 || hd == 128, "attn_decode_batch: head dim must be 64 or 128");
+    KD_CHECK_SHAPE(hdp >= hd && hdp % 8 == 0, "attn_decode_batch: hdp must be >= hd and a multiple of 8");
+    KD_CHECK_SHAPE(H > 0 && HKV > 0 && H % HKV == 0, "attn_decode_batch: heads must be a multiple of kv heads");
+    KD_CHECK_SHAPE(smax > 0 && smax <= MAX_CH * CH, "attn_decode_batch: need 0 < smax <= 32768");
+    KD_CHECK_ALIGN(q, 16, "attn_decode_batch: q misaligned");
+    KD_CHECK_ALIGN(kc, 16, "attn_decode_batch: k cache misaligned");
+    KD_CHECK_ALIGN(k_new, 16, "attn_decode_batch: k_new misaligned");
+    if (ws_bytes < attn_decode_batch_ws(nb, H, hd, smax))
+        return fail(KD_ERR_WORKSPACE, "attn_decode_batch: workspace too small");
+    const int nch = (smax + CH - 1) / CH, ngrp = (H / HKV + AB_R - 1) / AB_R;   // head groups per kv head
+    const float scale = 1.0f / sqrtf((float)hd);
+    hipStream_t s = as_stream(stream);
+    float* part = (float*)ws;
+    if (hd == 64) {
+        hipLaunchKernelGGL(k_attn_decode_part_batch<64>, dim3(HKV * ngrp, nch, nb), dim3(NT), 0, s, (const bf16*)q,
+                           (const bf16*)k_new, (const bf16*)v_new, (bf16*)kc, (bf16*)vc, part, H, HKV, hdp, smax, nb,
+                           cur_dev, scale);
+        hipLaunchKernelGGL(k_attn_decode_combine<64>, dim3(nb * H), dim3(NT), 0, s, part, nch, (bf16*)o);
+    } else {
+        hipLaunchKernelGGL(k_attn_decode_part_batch<128>, dim3(HKV * ngrp, nch, nb), dim3(NT), 0, s, (const bf16*)q,
+                           (const bf16*)k_new, (const bf16*)v_new, (bf16*)kc, (bf16*)vc, part, H, HKV, hdp, smax, nb,
+                           cur_dev, scale);
+        hipLaunchKernelGGL(k_attn_decode_combine<128>, dim3(nb * H), dim3(NT), 0, s, part, nch, (bf16*)o);
+    }
+    KD_LAUNCH_CHECK("k_attn_decode_batch");
+    return KD_OK;
+}
+
+int launch_gen_select_batch(const void* logits, int64_t ldl, int V, int64_t* seq, int smax, int nb, int* cur_dev,
+                            float penalty, int ngram, void* flags_ws, size_t ws_bytes, int64_t* out, void* stream) {
+    KD_CHECK_ARG(logits && seq && cur_dev && flags_ws, "gen_select_batch: null pointer");
+    KD_CHECK_SHAPE(V > 0 && smax > 0 && ldl >= V && nb >= 1 && nb <= GB_ROWS,
+                   "gen_select_batch: V, smax positive, ld >= V, 1 <= nb <= 16");
+    KD_CHECK_ARG(penalty > 0.f && ngram >= 0, "gen_select_batch: penalty must be > 0 and ngram >= 0");
+    if (ws_bytes < (size_t)nb * V) return fail(KD_ERR_WORKSPACE, "gen_select_batch: workspace must hold nb * V bytes");
+    hipLaunchKernelGGL(k_gen_select_batch, dim3(nb), dim3(1024), 0, as_stream(stream), (const bf16*)logits, ldl, V, seq,
+                       smax, cur_dev, penalty, ngram, (uint8_t*)flags_ws, out);
+    KD_LAUNCH_CHECK("k_gen_select_batch");
+    return KD_OK;
+}
+
+int launch_rope_rows(const float* cos_t, const float* sin_t, int hh, int rows, int nb, const int* cur_dev,
+                     float* cos_rows, float* sin_rows, void* stream) {
+    KD_CHECK_ARG(cos_t && sin_t && cur_dev && cos_rows && sin_rows, "rope_rows: null pointer");
+    KD_CHECK_SHAPE(hh > 0 && rows > 0 && nb >= 1 && nb <= GB_ROWS, "rope_rows: hh, rows positive, 1 <= nb <= 16");
+    hipLaunchKernelGGL(k_rope_rows, dim3(nb), dim3(256), 0, as_stream(stream), cos_t, sin_t, hh, rows, cur_dev, cos_rows,
+                       sin_rows);
+    KD_LAUNCH_CHECK("k_rope_rows");
+    return KD_OK;
+}
 
 int launch_rope_row(const float* cos_t, const float* sin_t, int hh, const int* cur_dev, float* cos_row, float* sin_row,
                     void* stream) {

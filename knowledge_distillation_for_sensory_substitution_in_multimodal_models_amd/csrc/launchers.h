@@ -67,6 +67,17 @@ int launch_gen_select(const void* logits, int V, int64_t* seq, int len, int* cur
                       void* flags_ws, size_t ws_bytes, int64_t* out, void* stream);
 int launch_rope_row(const float* cos_t, const float* sin_t, int hh, const int* cur_dev, float* cos_row, float* sin_row,
                     void* stream);
+size_t gemv_batch_ws(int N, int K, int epi);
+int launch_gemv_batch(const void* x, int64_t ldx, int nb, const void* W, int64_t ldw, const void* extra, void* y, int N,
+                      int K, int epi, int I, const void* norm_w, float eps, void* ws, size_t ws_bytes, void* stream);
+size_t attn_decode_batch_ws(int nb, int H, int hd, int smax);
+int launch_attn_decode_batch(const void* q, const void* k_new, const void* v_new, void* kc, void* vc, void* o, int nb,
+                             int H, int HKV, int hd, int hdp, int smax, const int* cur_dev, void* ws, size_t ws_bytes,
+                             void* stream);
+int launch_gen_select_batch(const void* logits, int64_t ldl, int V, int64_t* seq, int smax, int nb, int* cur_dev,
+                            float penalty, int ngram, void* flags_ws, size_t ws_bytes, int64_t* out, void* stream);
+int launch_rope_rows(const float* cos_t, const float* sin_t, int hh, int rows, int nb, const int* cur_dev,
+                     float* cos_rows, float* sin_rows, void* stream);
 int launch_image_resize(const uint8_t* in, int H, int W, uint8_t* out, int oh, int ow, void* ws, size_t ws_bytes,
                         void* stream);
 int launch_anyres_tiles(const uint8_t* base, const uint8_t* resized, int nh, int nw, int bh, int bw, int patch,

@@ -16,6 +16,10 @@ every launch of a step has fixed arguments: the first step runs eagerly, the ste
 once as a HIP graph (torch.cuda.CUDAGraph) and replayed for the rest; steps past an EOS are
 discarded afterwards (one host read at the end instead of one per token).  Returns prompt + generated ids like
 transformers' generate (B = 1, as the evaluation runs it).
+
+generate_batch() decodes up to 16 such prompts per step (ragged lengths, per-row device counters,
+batch-invariant kernels): the evaluation's one-question-at-a-time loop with the weights streamed
+once per step for all rows.
 """
 from __future__ import annotations
 
@@ -137,3 +141,133 @@ def generate(model, input_ids: torch.Tensor, pixel_values: torch.Tensor, image_s
             steps = steps[:n - L]
     out = seq[:n].view(1, n)
     return (out, steps) if return_logits else out
+
+
+MAX_BATCH = 16   # rows per decode step: the M dimension of the MFMA behind kd_gemv_batch
+
+
+@torch.no_grad()
+def generate_batch(model, prompts, max_new_tokens: int = 32, repetition_penalty: float = 1.0,
+                   no_repeat_ngram_size: int = 0, eos_token_id=EOS_TOKEN_IDS, pad_token_id: int | None = None,
+                   temperature: float | None = None, return_logits: bool = False, graph: bool = True):
+    """generate() for several prompts at once: prompts is a sequence of (input_ids [1, L_i],
+    pixel_values [1, P_i, 3, 384, 384], image_sizes [1, 2]), ragged in L_i and P_i (no padding, no
+    attention mask) -> list of int64 [1, L_i + n_i] (and, with return_logits, a list per row of the
+    bf16 logits row of every step).
+
+    Each prompt is prefilled on its own, exactly as generate() prefills it (the training forward's
+    GEMM plan depends on M, so a batched prefill would make a row depend on its neighbours); the
+    decode steps then run up to MAX_BATCH rows through every layer at once, so a step streams the
+    weights once for all rows (kd_gemv_batch / kd_attn_decode_batch / kd_gen_select_batch, per-row
+    lengths in a device counter).  A row's tokens and logits do not depend on which other prompts
+    share its batch (bit-identical), longer lists run in chunks of MAX_BATCH.  All rows run
+    max_new_tokens steps; each is cut after its first EOS with one host read at the end."""
+    del temperature, pad_token_id   # greedy; finished rows are cut, not padded
+    prompts = list(prompts)
+    if not prompts:
+        raise ValueError("generate_batch: no prompts")
+    if int(max_new_tokens) < 1:
+        raise ValueError("generate_batch: max_new_tokens must be >= 1")
+    for ids, _, _ in prompts:
+        if ids.dim() != 2 or ids.shape[0] != 1:
+            raise ValueError("generate_batch: every prompt's input_ids must be [1, L]")
+    outs, logs = [], []
+    for c0 in range(0, len(prompts), MAX_BATCH):
+        o, lg = _generate_rows(model, prompts[c0:c0 + MAX_BATCH], int(max_new_tokens), repetition_penalty,
+                               no_repeat_ngram_size, eos_token_id, return_logits, graph)
+        outs += o
+        logs += lg
+    return (outs, logs) if return_logits else outs
+
+
+def _generate_rows(model, prompts, max_new_tokens, repetition_penalty, no_repeat_ngram_size, eos_token_id,
+                   return_logits, graph):
+    T, P = model.cfg.text, model.P
+    dev = model.device
+    nb = len(prompts)
+    Ls = [int(ids.shape[1]) for ids, _, _ in prompts]
+    smax = max(Ls) + max_new_tokens
+    eos = {int(e) for e in ([eos_token_id] if isinstance(eos_token_id, int) else (eos_token_id or ()))}
+    nq, nkv, hd = T.heads, T.kv_heads, T.head_dim
+    qd, kd = nq * hd, nkv * hd
+    lp = "language_model.model."
+
+    # ---- prefill, one prompt at a time: generate()'s own (row b of the caches and of seq)
+    kc = torch.empty((T.layers, nb, nkv, smax, hd), dtype=torch.bfloat16, device=dev)
+    vc = torch.empty_like(kc)
+    seq = torch.zeros((nb, smax), dtype=torch.int64, device=dev)
+    steps = [[] for _ in range(nb)]
+    for b, (input_ids, pixel_values, image_sizes) in enumerate(prompts):
+        L = Ls[b]
+        kv = []
+        fwd = model.forward(input_ids, pixel_values, image_sizes, save=False, kv_out=kv)
+        for i, (k, v) in enumerate(kv):
+            kc[i, b, :, :L].copy_(k[0])
+            vc[i, b, :, :L].copy_(v[0])
+        del kv
+        seq[b, :L].copy_(input_ids[0])
+        logits = model.logits(fwd["hn"][L - 1:L])
+        del fwd
+        if return_logits:
+            steps[b].append(logits)
+        ops.gen_select(logits, seq[b], L, repetition_penalty, no_repeat_ngram_size)
+
+    cos, sin = model._rope_for(smax)
+    src = torch.full((nb,), -2, dtype=torch.int32, device=dev)   # token embedding (kd_embed_assemble)
+    table = P[lp + "embed_tokens.weight"]
+    layers = []
+    for i in range(T.layers):
+        p = f"{lp}layers.{i}."
+        layers.append((P[p + "input_layernorm.weight"],
+                       P.span(p + "self_attn.q_proj.weight", p + "self_attn.v_proj.weight", qd + 2 * kd, T.hidden),
+                       P.span(p + "self_attn.q_proj.bias", p + "self_attn.v_proj.bias", 1, qd + 2 * kd).view(-1),
+                       P[p + "self_attn.o_proj.weight"], P[p + "post_attention_layernorm.weight"],
+                       P.span(p + "mlp.gate_proj.weight", p + "mlp.up_proj.weight", 2 * T.inter, T.hidden),
+                       P[p + "mlp.down_proj.weight"]))
+    # device-resident per-row step state (generate()'s, one entry per row)
+    cur = torch.tensor([L + 1 for L in Ls], dtype=torch.int32, device=dev)
+    tok = torch.stack([seq[b, Ls[b]] for b in range(nb)])   # the tokens being decoded
+    cos_rows = torch.empty((nb, cos.shape[1]), dtype=torch.float32, device=dev)
+    sin_rows = torch.empty_like(cos_rows)
+
+    def step():
+        ops.rope_rows(cos, sin, cur, cos_rows, sin_rows)
+        x = ops.embed_assemble(tok, src, table, None, None, model.err)
+        for i, (w_in, Wqkv, bqkv, Wo, w_post, Wgu, Wdown) in enumerate(layers):
+            qkv = ops.gemv_batch(x, Wqkv, bias=bqkv, norm_w=w_in, eps=T.eps)      # input_layernorm fused
+            q, k, v = ops.qkv_split(qkv, 1, nb, nq, nkv, hd, hd, cos_rows, sin_rows)   # token b rotated by row b
+            o = ops.attn_decode_batch(q[0], k[0], v[0], kc[i], vc[i], cur, hd)
+            x_mid = ops.gemv_batch(o, Wo, residual=x)
+            a = ops.gemv_batch(x_mid, Wgu, swiglu_inter=T.inter, norm_w=w_post, eps=T.eps)  # post_attention_layernorm
+            x = ops.gemv_batch(a, Wdown, residual=x_mid)
+        hn, _, _ = ops.norm_fwd(x, P[lp + "norm.weight"], None, T.eps, rms=True, save_stats=False)
+        lg = ops.gemv_batch(hn, model.lm_head_weight())
+        ops.gen_select_batch(lg, seq, cur, repetition_penalty, no_repeat_ngram_size, out=tok)
+        return lg
+
+    graph_obj = None
+    for t_ in range(max_new_tokens - 1):
+        if graph and t_ == 1:   # step 0 ran eagerly (warm-up: allocations, workspaces); capture the rest
+            graph_obj = torch.cuda.CUDAGraph()
+            with torch.cuda.graph(graph_obj):
+                lg_static = step()
+        if graph_obj is not None:
+            graph_obj.replay()
+            lg = lg_static
+        else:
+            lg = step()
+        if return_logits:
+            lg = lg.clone()
+            for b in range(nb):
+                steps[b].append(lg[b:b + 1])
+    ends = [L + max_new_tokens for L in Ls]
+    if eos:   # every row is cut after its own first EOS; the steps past it are discarded
+        host = seq.tolist()
+        for b, L in enumerate(Ls):
+            for j, t_ in enumerate(host[b][L:ends[b]]):
+                if t_ in eos:
+                    ends[b] = L + j + 1
+                    break
+            steps[b] = steps[b][:ends[b] - L]
+    outs = [seq[b, :ends[b]].view(1, ends[b]) for b in range(nb)]
+    return outs, (steps if return_logits else [])

@@ -773,3 +773,88 @@ def rope_row(cos: torch.Tensor, sin: torch.Tensor, cur: torch.Tensor, cos_row: t
     """cos/sin row of position cur[0] - 1 into the one-row buffers (kd_rope_row)."""
     NV.call("kd_rope_row", cos.data_ptr(), sin.data_ptr(), cos.shape[1], cur.data_ptr(), cos_row.data_ptr(),
             sin_row.data_ptr(), _stream())
+
+
+# ------------------------------------------------------------ batched decode ----
+def rope_rows(cos: torch.Tensor, sin: torch.Tensor, cur: torch.Tensor, cos_rows: torch.Tensor,
+              sin_rows: torch.Tensor):
+    """cos/sin row of position cur[b] - 1 into row b of the [nb, hh] buffers (kd_rope_rows)."""
+    _require(cur, torch.int32, "rope_rows.cur")
+    nb = cur.numel()
+    if cos_rows.shape != (nb, cos.shape[1]) or sin_rows.shape != cos_rows.shape:
+        raise RuntimeError("rope_rows: cos_rows / sin_rows must be [nb, hh]")
+    NV.call("kd_rope_rows", cos.data_ptr(), sin.data_ptr(), cos.shape[1], cos.shape[0], nb, cur.data_ptr(),
+            cos_rows.data_ptr(), sin_rows.data_ptr(), _stream())
+
+
+def gemv_batch(x: torch.Tensor, w: torch.Tensor, *, bias=None, residual=None, swiglu_inter: int = 0, norm_w=None,
+               eps: float = 1e-6) -> torch.Tensor:
+    """nb <= 16 token rows through a linear layer (kd_gemv_batch): x [nb, K] bf16, w [N, K] (row
+    stride may exceed K) -> [nb, N] bf16, epilogues and the fused RMSNorm as gemv().  Row b of the
+    result does not depend on nb or on the other rows (bit-identical to the nb = 1 call)."""
+    _require(x, torch.bfloat16, "gemv_batch.x")
+    if x.dim() != 2 or x.stride(1) != 1:
+        raise RuntimeError("gemv_batch: x must be [nb, K] with a contiguous last dim")
+    nb, K = x.shape
+    epi, extra = 0, None
+    if swiglu_inter:
+        epi, N = 3, int(swiglu_inter)
+    else:
+        N = w.shape[0]
+        if bias is not None:
+            epi, extra = 1, bias
+        elif residual is not None:
+            epi, extra = 2, residual
+            if residual.shape != (nb, N) or not residual.is_contiguous():
+                raise RuntimeError("gemv_batch: residual must be a contiguous [nb, N] tensor")
+    y = torch.empty((nb, N), dtype=torch.bfloat16, device=x.device)
+    nbytes = NV.lib().kd_gemv_batch_workspace_size(N, K, epi)
+    ws = _workspace(("gemv_batch", _stream()), nbytes, x.device) if nbytes else None
+    NV.call("kd_gemv_batch", x.data_ptr(), max(x.stride(0), K), nb, w.data_ptr(), w.stride(0), _ptr(extra),
+            y.data_ptr(), N, K, epi, int(swiglu_inter), _ptr(norm_w), float(eps), _ptr(ws),
+            0 if ws is None else ws.numel(), _stream())
+    return y
+
+
+def attn_decode_batch(q: torch.Tensor, k_new: torch.Tensor, v_new: torch.Tensor, k_cache: torch.Tensor,
+                      v_cache: torch.Tensor, cur: torch.Tensor, hd: int, out: torch.Tensor | None = None) -> torch.Tensor:
+    """One token per row against that row's cache positions [0, cur[b]) (kd_attn_decode_batch).
+    q [H, nb, hdp], k_new/v_new [HKV, nb, hdp] (qkv_split(B=1, S=nb)), caches [nb, HKV, smax, hdp],
+    cur [nb] int32 -> o [nb, H*hd] bf16; row b's k_new/v_new are stored at cur[b] - 1."""
+    H, nb, hdp = q.shape
+    nb2, HKV, smax, _ = k_cache.shape
+    _require(cur, torch.int32, "attn_decode_batch.cur")
+    if nb2 != nb or cur.numel() != nb or k_new.shape != (HKV, nb, hdp) or v_new.shape != k_new.shape:
+        raise RuntimeError("attn_decode_batch: q [H, nb, hdp], k_new/v_new [HKV, nb, hdp], caches [nb, HKV, smax, hdp]")
+    for t, n in ((q, "q"), (k_new, "k_new"), (v_new, "v_new"), (k_cache, "k_cache"), (v_cache, "v_cache")):
+        _require(t, torch.bfloat16, f"attn_decode_batch.{n}")
+        if not t.is_contiguous():
+            raise RuntimeError(f"attn_decode_batch: {n} must be contiguous")
+    if out is None:
+        out = torch.empty((nb, H * hd), dtype=torch.bfloat16, device=q.device)
+    nbytes = NV.lib().kd_attn_decode_batch_workspace_size(nb, H, hd, smax)
+    ws = _workspace(("attn_decode_batch", _stream()), nbytes, q.device)
+    NV.call("kd_attn_decode_batch", q.data_ptr(), k_new.data_ptr(), v_new.data_ptr(), k_cache.data_ptr(),
+            v_cache.data_ptr(), out.data_ptr(), nb, H, HKV, hd, hdp, smax, cur.data_ptr(), ws.data_ptr(), ws.numel(),
+            _stream())
+    return out
+
+
+def gen_select_batch(logits: torch.Tensor, seq: torch.Tensor, cur: torch.Tensor, repetition_penalty: float = 1.0,
+                     no_repeat_ngram_size: int = 0, out: torch.Tensor | None = None) -> None:
+    """gen_select per row (kd_gen_select_batch): logits [nb, V] bf16, seq [nb, smax] int64, cur [nb]
+    int32; writes seq[b, cur[b]], out[b] and cur[b] += 1."""
+    _require(logits, torch.bfloat16, "gen_select_batch.logits")
+    _require(seq, torch.int64, "gen_select_batch.seq")
+    _require(cur, torch.int32, "gen_select_batch.cur")
+    nb, V = logits.shape
+    if logits.stride(1) != 1 or seq.dim() != 2 or seq.shape[0] != nb or not seq.is_contiguous() or cur.numel() != nb:
+        raise RuntimeError("gen_select_batch: logits [nb, V], seq contiguous [nb, smax], cur [nb]")
+    if out is not None:
+        _require(out, torch.int64, "gen_select_batch.out")
+        if out.numel() != nb or not out.is_contiguous():
+            raise RuntimeError("gen_select_batch: out must be a contiguous [nb] tensor")
+    ws = _workspace(("gen_select_batch", _stream()), nb * V, logits.device)
+    NV.call("kd_gen_select_batch", logits.data_ptr(), max(logits.stride(0), V), V, seq.data_ptr(), seq.shape[1], nb,
+            cur.data_ptr(), float(repetition_penalty), int(no_repeat_ngram_size), ws.data_ptr(), ws.numel(), _ptr(out),
+            _stream())

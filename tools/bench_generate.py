@@ -1,6 +1,10 @@
 """Time the student generate() (evaluate_onevision.py:185-195 settings) on the real 0.5B student:
 prefill of one 336x336 prompt (L = 1536) + 32 greedy decode steps with the KV cache.
-    python tools/bench_generate.py"""
+    python tools/bench_generate.py
+    python tools/bench_generate.py --batch 16    also generate_batch() at nb in {1, 2, 4, 8, 16} <= 16:
+                                                 the batched step against the single-prompt step
+                                                 measured in the same process"""
+import argparse
 import sys
 import time
 from pathlib import Path
@@ -9,9 +13,15 @@ import torch
 
 sys.path.insert(0, str(Path(__file__).resolve().parent.parent))
 from knowledge_distillation_for_sensory_substitution_in_multimodal_models_amd.data import synthetic_batch  # noqa
-from knowledge_distillation_for_sensory_substitution_in_multimodal_models_amd.generation import generate  # noqa
+from knowledge_distillation_for_sensory_substitution_in_multimodal_models_amd.generation import (  # noqa
+    generate, generate_batch)
 from knowledge_distillation_for_sensory_substitution_in_multimodal_models_amd.modeling import (  # noqa
     STUDENT_05B, LlavaOnevisionModel)
+
+ap = argparse.ArgumentParser()
+ap.add_argument("--batch", type=int, default=0, metavar="N",
+                help="also time generate_batch() at every nb in {1, 2, 4, 8, 16} up to N")
+args = ap.parse_args()
 
 dev = torch.device("cuda:0")
 model = LlavaOnevisionModel(STUDENT_05B, dev, seed=2)
@@ -19,16 +29,21 @@ b = synthetic_batch(1, dev, L=1536, seed=0)
 kw = dict(repetition_penalty=1.2, no_repeat_ngram_size=2, eos_token_id=())
 
 
-def timed(n_new):
-    generate(model, b["depth_input_ids"], b["depth_pixel_values"], b["image_sizes"], max_new_tokens=n_new, **kw)
+def best_of(fn, reps=3):
+    fn()
     torch.cuda.synchronize()
     best = 1e30
-    for _ in range(3):
+    for _ in range(reps):
         t0 = time.perf_counter()
-        generate(model, b["depth_input_ids"], b["depth_pixel_values"], b["image_sizes"], max_new_tokens=n_new, **kw)
+        fn()
         torch.cuda.synchronize()
         best = min(best, time.perf_counter() - t0)
     return best
+
+
+def timed(n_new):
+    return best_of(lambda: generate(model, b["depth_input_ids"], b["depth_pixel_values"], b["image_sizes"],
+                                    max_new_tokens=n_new, **kw))
 
 
 t32, t96 = timed(32), timed(96)
@@ -36,6 +51,22 @@ t0 = time.perf_counter()
 model.forward(b["depth_input_ids"], b["depth_pixel_values"], b["image_sizes"])
 torch.cuda.synchronize()
 pre = time.perf_counter() - t0
+step1 = (t96 - t32) / 64 * 1e3
 print(f"generate 0.5B student, 336x336 prompt (L=1536) + 32 tokens: {t32 * 1e3:.1f} ms per call "
-      f"(prefill forward {pre * 1e3:.1f} ms); graph-replayed decode step {(t96 - t32) / 64 * 1e3:.3f} ms/token "
+      f"(prefill forward {pre * 1e3:.1f} ms); graph-replayed decode step {step1:.3f} ms/token "
       f"(marginal cost from 32 -> 96 new tokens)")
+
+if args.batch > 0:
+    # distinct 336x336 prompts (different seeds, L = 1536 each: every row's cache is as long as the
+    # single-prompt run's); the marginal step cost from 32 -> 96 new tokens as above
+    rows = [synthetic_batch(1, dev, L=1536, seed=s) for s in range(min(args.batch, 16))]
+    prompts = [(r["depth_input_ids"], r["depth_pixel_values"], r["image_sizes"]) for r in rows]
+    print(f"generate_batch, same process: single-prompt step {step1:.3f} ms/token")
+    for nb in (1, 2, 4, 8, 16):
+        if nb > args.batch:
+            break
+        tb = [best_of(lambda: generate_batch(model, prompts[:nb], max_new_tokens=n, **kw)) for n in (32, 96)]
+        step = (tb[1] - tb[0]) / 64 * 1e3
+        print(f"  nb={nb:2d}: {tb[0] * 1e3:7.1f} ms per call of 32 tokens; decode step {step:.3f} ms/step = "
+              f"{step / nb:.3f} ms/token/row ({step / step1:.2f}x the single-prompt step, "
+              f"{step1 * nb / step:.2f}x its tokens/s)")
