@@ -486,7 +486,7 @@ int kd_rope_row(const float* cos_table, const float* sin_table, int hh, const in
  *   workspace >= nb * V bytes.
  * kd_rope_rows: cos/sin row of position cur_dev[b] - 1 of the [table_rows, hh] tables into row b
  *   of [nb, hh] buffers: as kd_qkv_split's tables with (B = 1, S = nb) they rotate token b by its
- *   own position. */
+ *   own position (nb <= KD_GEMV_ROWS_MAX: the grouped prefill below rotates all its rows at once). */
 size_t kd_gemv_batch_workspace_size(int N, int K, int epilogue);
 int kd_gemv_batch(const void* x, int64_t ldx, int nb, const void* W, int64_t ldw, const void* extra, void* y, int N,
                   int K, int epilogue, int inter, const void* norm_w, float eps, void* workspace,
@@ -500,6 +500,38 @@ int kd_gen_select_batch(const void* logits, int64_t ld_logits, int V, int64_t* s
                         size_t workspace_bytes, int64_t* out, void* stream);
 int kd_rope_rows(const float* cos_table, const float* sin_table, int hh, int table_rows, int nb,
                  const int32_t* cur_dev, float* cos_rows, float* sin_rows, void* stream);
+
+/* Grouped prefill (generate_grouped()): the question rows behind a shared image prefix.  The prefix
+ * runs once through kd_model_forward and seeds the cache of every question of its image; the
+ * ragged suffix rows of up to 16 questions then go through the layers together on the two entry
+ * points below, before the batched decode above takes over.  Both are batch invariant in the
+ * sense above: a row's bits depend on its own question alone.
+ * kd_gemv_rows: kd_gemv_batch for 1 <= rows <= KD_GEMV_ROWS_MAX rows; a workgroup reads its
+ *   weight fragments once per launch and keeps them in registers across its 16-row slabs of x
+ *   (the slabs of a weight tile are shared out among at most 4 workgroups).  Same arguments, same
+ *   epilogues (`extra` = the residual [rows, N] for 2) and fused norm; row r of y [rows, N] is
+ *   bit-identical to kd_gemv_batch on row r alone: every slab runs under the (N, K) plan and in
+ *   the arithmetic order of kd_gemv_batch.  Shapes with N > 32752 (one weight tile per wave: the
+ *   lm_head) make one kd_gemv_batch pass per slab instead.  kd_gemv_rows_workspace_size(rows, N,
+ *   K, epilogue) bytes of workspace; with rows = 16 that is kd_gemv_batch_workspace_size.
+ * kd_attn_extend: question b owns rows [row_start[b], row_start[b + 1]) of q [H, rows, hdp] and
+ *   k_new / v_new [HKV, rows, hdp] (kd_qkv_split with B = 1, S = rows: every row roped at its own
+ *   position); its row j sits at position base[b] + j and attends to positions [0, base[b]) of the
+ *   question's cache ([nb, HKV, smax, hdp], already filled) and to its own question's rows 0..j
+ *   (read from k_new / v_new); o [rows, H * hd] bf16, scale hd^-0.5, fp32 softmax.  The question's
+ *   k_new / v_new rows are stored at cache positions [base[b], base[b] + S_b); no other cache
+ *   element is written and none of those is read by the call.  row_start [nb + 1] and base [nb]
+ *   are device int32 with row_start[0] = 0 and row_start[nb] = rows.  A question with S_b < 1 or
+ *   base[b] + S_b > smax touches no cache (its rows of o are then undefined). */
+#define KD_GEMV_ROWS_MAX 1024
+size_t kd_gemv_rows_workspace_size(int rows, int N, int K, int epilogue);
+int kd_gemv_rows(const void* x, int64_t ldx, int rows, const void* W, int64_t ldw, const void* extra, void* y,
+                 int N, int K, int epilogue, int inter, const void* norm_w, float eps, void* workspace,
+                 size_t workspace_bytes, void* stream);
+size_t kd_attn_extend_workspace_size(int rows, int H, int hd, int smax);
+int kd_attn_extend(const void* q, const void* k_new, const void* v_new, void* k_cache, void* v_cache, void* o,
+                   int nb, int rows, int H, int HKV, int hd, int hdp, int smax, const int32_t* row_start,
+                   const int32_t* base, void* workspace, size_t workspace_bytes, void* stream);
 
 /* --------------------------------------------------------- model runtime ---- */
 /* One LLaVA-OneVision instance (SigLIP -> projector -> anyres pack -> Qwen2 -> lm_head)

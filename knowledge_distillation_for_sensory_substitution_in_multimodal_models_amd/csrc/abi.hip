@@ -179,6 +179,17 @@ int kd_rope_rows(const float* c, const float* sn, int hh, int rows, int nb, cons
                  void* s) {
     return kd::launch_rope_rows(c, sn, hh, rows, nb, cur, cr, sr, s);
 }
+size_t kd_gemv_rows_workspace_size(int rows, int N, int K, int epi) { return kd::gemv_rows_ws(rows, N, K, epi); }
+int kd_gemv_rows(const void* x, int64_t ldx, int rows, const void* W, int64_t ldw, const void* extra, void* y, int N,
+                 int K, int epi, int I, const void* norm_w, float eps, void* ws, size_t wsb, void* s) {
+    return kd::launch_gemv_rows(x, ldx, rows, W, ldw, extra, y, N, K, epi, I, norm_w, eps, ws, wsb, s);
+}
+size_t kd_attn_extend_workspace_size(int rows, int H, int hd, int smax) { return kd::attn_extend_ws(rows, H, hd, smax); }
+int kd_attn_extend(const void* q, const void* kn, const void* vn, void* kc, void* vc, void* o, int nb, int rows, int H,
+                   int HKV, int hd, int hdp, int smax, const int32_t* row_start, const int32_t* base, void* ws,
+                   size_t wsb, void* s) {
+    return kd::launch_attn_extend(q, kn, vn, kc, vc, o, nb, rows, H, HKV, hd, hdp, smax, row_start, base, ws, wsb, s);
+}
 size_t kd_image_resize_workspace_size(int H, int W, int oh, int ow) { return kd::image_resize_ws(H, W, oh, ow); }
 int kd_image_resize_u8(const uint8_t* in, int H, int W, uint8_t* out, int oh, int ow, void* ws, size_t ws_bytes,
                        void* s) {

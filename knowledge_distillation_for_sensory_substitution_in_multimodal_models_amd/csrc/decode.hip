@@ -14,7 +14,9 @@
 //                   device-resident sequence (no host sync per token).
 // and their batched forms for generate_batch() (up to 16 prompts per step, per-row lengths on the
 // device, batch-invariant): k_gemv_batch (bf16 MFMA, the batch as M), k_attn_decode_part_batch,
-// k_gen_select_batch, k_rope_rows.
+// k_gen_select_batch, k_rope_rows; and for generate_grouped() (one image prefill shared by its
+// questions) the suffix rows of a chunk: k_gemv_slabs (k_gemv_batch for more than 16 rows, row for
+// row the same bits) and k_attn_extend_part (ragged suffix queries against prefix + own suffix).
 #include "common.h"
 
 #include <algorithm>
@@ -663,6 +665,299 @@ __global__ void k_rope_rows(const float* __restrict__ cos_t, const float* __rest
     }
 }
 
+
+// ------------------------------------------- grouped prefill: the suffix rows of a chunk ----
+// k_gemv_batch for rows > 16 (kd_gemv_rows): the workgroup of a wave_n = 0 plan loads its wave's
+// share of the weight tile once -- at most GB_MAX_STEPS / 4 fragments per wave, kept in VGPRs
+// (compile-time indices, wave-uniform guards) -- and loops over its 16-row slabs of x, staging
+// each slab (and its norm) as k_gemv_batch does.  Every slab runs k_gemv_batch's arithmetic in
+// k_gemv_batch's order (32-k steps interleaved over the waves in ascending order, wave-order LDS
+// sum, slice-order K reduce, 16 lanes per row for the norm), so a row's result is bit-identical
+// to kd_gemv_batch on that row alone.  The partials of a split K are [ksplit, NACC, rows16, N].
+constexpr int GS_FR = GB_MAX_STEPS / (NT / 64);   // weight fragments per wave and operand
+constexpr int GS_SLAB_GROUPS = 4;                 // workgroups per weight tile, each with every 4th slab
+
+template <int EPI>
+__global__ void __launch_bounds__(NT) k_gemv_slabs(const bf16* __restrict__ x, int64_t ldx, const bf16* __restrict__ W,
+                                                   int64_t ldw, const bf16* __restrict__ extra, bf16* __restrict__ y,
+                                                   float* __restrict__ part, int rows, int N, int K, int I,
+                                                   const bf16* __restrict__ norm_w, float eps, int slice_steps,
+                                                   int ksplit) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char gb_smem[];
+    constexpr int NACC = EPI == 3 ? 2 : 1;
+    __shared__ float rstd_s[GB_ROWS];
+    __shared__ f32x4 red_s[NACC][NT / 64][64];
+    bf16* xs = (bf16*)gb_smem;
+    const int w = threadIdx.x >> 6, lane = threadIdx.x & 63, ks = blockIdx.y;
+    const int ksteps = (K + 31) >> 5;
+    const int s_beg = ks * slice_steps, s_end = min(ksteps, s_beg + slice_steps);
+    const int kb = s_beg * 32, XLD = slice_steps * 32 + GB_PAD;
+    const bf16x8 zero8 = {};
+    const int col = lane & 15, kq = (lane >> 4) * 8;
+    const int n = blockIdx.x * 16 + col, nc = min(n, N - 1);   // rows past N: a valid row is read, nothing stored
+    const bf16* r0 = W + (size_t)nc * ldw;
+    const bf16* r1 = W + (size_t)(I + nc) * ldw;
+    const int s_first = s_beg + w, sst = NT / 64;
+    // the wave's whole share of the weight tile, once per launch; loads past the share or the K
+    // tail stay unconditional, on the row's first chunk, and are replaced by zeros
+    bf16x8 f0[GS_FR], f1[EPI == 3 ? GS_FR : 1];
+#pragma unroll
+    for (int i = 0; i < GS_FR; ++i) {
+        const int k = (s_first + i * sst) * 32 + kq;
+        const bool in = s_first + i * sst < s_end && k < K;
+        const bf16x8 l0 = *(const bf16x8*)(r0 + (in ? k : 0));
+        f0[i] = in ? l0 : zero8;
+        if constexpr (EPI == 3) {
+            const bf16x8 l1 = *(const bf16x8*)(r1 + (in ? k : 0));
+            f1[i] = in ? l1 : zero8;
+        }
+    }
+    const int rows16 = (rows + GB_ROWS - 1) / GB_ROWS * GB_ROWS;
+    const int cpr = slice_steps * 4;   // 16-B chunks per staged row
+    const bf16* xr = xs + col * XLD + kq - kb;
+    // slabs blockIdx.z, blockIdx.z + gridDim.z, ...: a slab is a chain of dependent round trips (norm,
+    // staging, MFMA, LDS sum), so up to GS_SLAB_GROUPS workgroups per tile share a CU and overlap them
+    for (int row0 = blockIdx.z * GB_ROWS; row0 < rows; row0 += gridDim.z * GB_ROWS) {
+        const bf16* xsl = x + (size_t)row0 * ldx;
+        const int nb = min(GB_ROWS, rows - row0);
+        if (norm_w) {   // per-row 1/rms over the whole row: 16 lanes per row, the same order in every slot
+            const int b = threadIdx.x >> 4, sub = threadIdx.x & 15;
+            float ss = 0.f;
+            if (b < nb) {
+                const bf16* xrow = xsl + (size_t)b * ldx;
+#pragma unroll 8
+                for (int k = sub * 8; k < K; k += 128) {
+                    const bf16x8 v = *(const bf16x8*)(xrow + k);
+#pragma unroll
+                    for (int e = 0; e < 8; ++e) ss += (float)v[e] * (float)v[e];
+                }
+            }
+#pragma unroll
+            for (int o = 8; o > 0; o >>= 1) ss += __shfl_xor(ss, o, 64);
+            if (sub == 0) rstd_s[b] = rsqrtf(ss / K + eps);
+            __syncthreads();
+        }
+#pragma unroll 4
+        for (int idx = threadIdx.x; idx < GB_ROWS * cpr; idx += NT) {
+            const int b = idx / cpr, c = idx - b * cpr, k = kb + c * 8;
+            const bool in = b < nb && k < K;   // else zeros: rows >= nb and the K tail
+            const int bc = min(b, nb - 1), kc8 = min(k, K - 8);   // the loads stay unconditional, inside x
+            bf16x8 v = *(const bf16x8*)(xsl + (size_t)bc * ldx + kc8);
+            if (norm_w) {
+                const bf16x8 nw = *(const bf16x8*)(norm_w + kc8);
+                const float rstd = rstd_s[bc];
+#pragma unroll
+                for (int e = 0; e < 8; ++e) v[e] = (bf16)((float)v[e] * rstd * (float)nw[e]);
+            }
+            *(bf16x8*)(xs + b * XLD + c * 8) = in ? v : zero8;
+        }
+        __syncthreads();
+        f32x4 acc0 = {0.f, 0.f, 0.f, 0.f}, acc1 = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+        for (int i = 0; i < GS_FR; ++i) {
+            const int s = s_first + i * sst;
+            if (s < s_end) {   // wave-uniform
+                const bf16x8 a = *(const bf16x8*)(xr + s * 32);
+                acc0 = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, f0[i], acc0, 0, 0, 0);
+                if constexpr (EPI == 3) acc1 = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, f1[i], acc1, 0, 0, 0);
+            }
+        }
+        red_s[0][w][lane] = acc0;
+        if constexpr (EPI == 3) red_s[1][w][lane] = acc1;
+        __syncthreads();   // also: every wave is done with xs and rstd_s before the next slab overwrites them
+        if (w != 0 || n >= N) continue;   // wave 0 passes the next slab's barriers before red_s is rewritten
+        acc0 = ((red_s[0][0][lane] + red_s[0][1][lane]) + red_s[0][2][lane]) + red_s[0][3][lane];
+        if constexpr (EPI == 3) acc1 = ((red_s[1][0][lane] + red_s[1][1][lane]) + red_s[1][2][lane]) + red_s[1][3][lane];
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {   // D: column n = lane & 15, slab row (lane >> 4) * 4 + r
+            const int b = (lane >> 4) * 4 + r;
+            if (b >= nb) continue;
+            const size_t gr = (size_t)row0 + b;
+            if (ksplit == 1) {
+                float v = acc0[r];
+                if constexpr (EPI == 1) v += (float)extra[n];
+                if constexpr (EPI == 2) v += (float)extra[gr * N + n];
+                if constexpr (EPI == 3) v = silu_fast(acc0[r]) * acc1[r];
+                y[gr * N + n] = (bf16)v;
+            } else {
+                part[(((size_t)ks * NACC) * rows16 + gr) * N + n] = acc0[r];
+                if constexpr (EPI == 3) part[(((size_t)ks * NACC + 1) * rows16 + gr) * N + n] = acc1[r];
+            }
+        }
+    }
+}
+
+// k_gemv_batch_reduce over `rows` rows of partials [ksplit, NACC, rows16, N]: grid (ceil(N / 256), rows).
+template <int EPI>
+__global__ void __launch_bounds__(NT) k_gemv_slabs_reduce(const float* __restrict__ part, const bf16* __restrict__ extra,
+                                                          bf16* __restrict__ y, int rows, int rows16, int N,
+                                                          int ksplit) {
+    constexpr int NACC = EPI == 3 ? 2 : 1;
+    const int b = blockIdx.y, n = blockIdx.x * NT + threadIdx.x;
+    if (b >= rows || n >= N) return;
+    float a0 = 0.f, a1 = 0.f;
+    for (int ks = 0; ks < ksplit; ++ks) {
+        a0 += part[(((size_t)ks * NACC) * rows16 + b) * N + n];
+        if constexpr (EPI == 3) a1 += part[(((size_t)ks * NACC + 1) * rows16 + b) * N + n];
+    }
+    float v = a0;
+    if constexpr (EPI == 1) v += (float)extra[n];
+    if constexpr (EPI == 2) v += (float)extra[(size_t)b * N + n];
+    if constexpr (EPI == 3) v = silu_fast(a0) * a1;
+    y[(size_t)b * N + n] = (bf16)v;
+}
+
+// Extend attention (kd_attn_extend): the ragged suffix rows of nb questions, each against its own
+// cache prefix [0, base) plus its own suffix rows up to itself.  Workgroup (kv head, 64-key chunk,
+// question): the chunk's K ([key][d]) and V (transposed, [d][key]) are staged in LDS once for all
+// S x R query-head rows of the question (row m = suffix row m / R, head m % R of the GQA group);
+// positions >= base come from k_new / v_new, never from the cache rows this launch writes (the
+// workgroup that owns a position stores it), positions past the suffix are zeros.  The waves take
+// the rows in tiles of 16 on v_mfma_f32_16x16x32_bf16 (operand layout of k_gemv_batch): Q K^T
+// (M = rows, N = 64 keys, K = HD), the chunk softmax in fp32 with key <= position, P (rounded to
+// bf16 through LDS; the row sum is taken over the rounded values) times V.  Partials
+// [rows * H, nch, HD + 2] for k_attn_decode_combine; chunk boundaries, tiles and order depend on
+// the question's own (base, S) only.
+constexpr int AE_PAD = 8;   // bf16 per LDS row: rows 16 B apart in the banks
+
+template <int HD>
+__global__ void __launch_bounds__(NT) k_attn_extend_part(const bf16* __restrict__ q, const bf16* __restrict__ k_new,
+                                                         const bf16* __restrict__ v_new, bf16* __restrict__ kc,
+                                                         bf16* __restrict__ vc, float* __restrict__ part, int H,
+                                                         int HKV, int hdp, int smax, int rows,
+                                                         const int* __restrict__ row_start,
+                                                         const int* __restrict__ base_dev, float scale) {
+    __shared__ __attribute__((aligned(16))) bf16 k_s[CH][HD + AE_PAD];
+    __shared__ __attribute__((aligned(16))) bf16 vt_s[HD][CH + AE_PAD];
+    __shared__ __attribute__((aligned(16))) bf16 p_s[NT / 64][16][CH + AE_PAD];
+    const int kvh = blockIdx.x, c = blockIdx.y, b = blockIdx.z, nch = gridDim.y;
+    const int R = H / HKV, j0 = c * CH;
+    const int rs0 = row_start[b], rs1 = row_start[b + 1], S = rs1 - rs0, base = base_dev[b];
+    if (rs0 < 0 || rs1 > rows || S < 1) return;   // the question owns no row
+    const int M = S * R;
+    const int w = threadIdx.x >> 6, lane = threadIdx.x & 63, col = lane & 15, quad = lane >> 4;
+    if (base < 0 || base > smax - S || j0 >= base + S) {   // no key of this chunk for any row (or no room in the cache)
+        for (int i = threadIdx.x; i < M * (HD + 2); i += NT) {
+            const int m = i / (HD + 2), e = i - m * (HD + 2), j = m / R, r = m - j * R;
+            part[(((size_t)(rs0 + j) * H + kvh * R + r) * nch + c) * (HD + 2) + e] = e == 0 ? -INFINITY : 0.f;
+        }
+        return;
+    }
+    bf16* K = kc + ((size_t)b * HKV + kvh) * smax * hdp;
+    bf16* V = vc + ((size_t)b * HKV + kvh) * smax * hdp;
+    const bf16* kn = k_new + ((size_t)kvh * rows + rs0) * hdp;
+    const bf16* vn = v_new + ((size_t)kvh * rows + rs0) * hdp;
+    constexpr int C8 = HD / 8;
+    for (int idx = threadIdx.x; idx < CH * C8; idx += NT) {
+        const int key = idx / C8, c8 = idx - key * C8, p = j0 + key;
+        bf16x8 k8 = {}, v8 = {};
+        if (p < base) {
+            k8 = *(const bf16x8*)(K + (size_t)p * hdp + c8 * 8);
+            v8 = *(const bf16x8*)(V + (size_t)p * hdp + c8 * 8);
+        } else if (p < base + S) {
+            k8 = *(const bf16x8*)(kn + (size_t)(p - base) * hdp + c8 * 8);
+            v8 = *(const bf16x8*)(vn + (size_t)(p - base) * hdp + c8 * 8);
+        }
+        *(bf16x8*)&k_s[key][c8 * 8] = k8;
+#pragma unroll
+        for (int e = 0; e < 8; ++e) vt_s[c8 * 8 + e][key] = v8[e];
+    }
+    {   // the suffix rows that fall into this chunk go into the caches (read by later launches only)
+        const int hc = hdp / 8;
+        for (int idx = threadIdx.x; idx < CH * hc; idx += NT) {
+            const int key = idx / hc, c8 = idx - key * hc, p = j0 + key;
+            if (p >= base && p < base + S) {
+                *(bf16x8*)(K + (size_t)p * hdp + c8 * 8) = *(const bf16x8*)(kn + (size_t)(p - base) * hdp + c8 * 8);
+                *(bf16x8*)(V + (size_t)p * hdp + c8 * 8) = *(const bf16x8*)(vn + (size_t)(p - base) * hdp + c8 * 8);
+            }
+        }
+    }
+    __syncthreads();
+    const int ntile = (M + 15) / 16;
+    for (int t0 = 0; t0 < ntile; t0 += NT / 64) {   // workgroup-uniform trip count (the barrier below)
+        const int t = t0 + w, m0 = t * 16;
+        const bool have = t < ntile;
+        // this lane's rows of D: m0 + quad * 4 + r
+        bool rv[4];
+        int pos[4];
+        size_t poff[4];
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+            const int m = m0 + quad * 4 + r, mc = min(m, M - 1), j = mc / R, rr = mc - j * R;
+            rv[r] = have && m < M;
+            pos[r] = base + j;
+            poff[r] = (((size_t)(rs0 + j) * H + kvh * R + rr) * nch + c) * (HD + 2);
+        }
+        // a tile whose last row sits before the chunk has no key here (wave-uniform)
+        const bool act = have && j0 <= base + min(m0 + 15, M - 1) / R;
+        float mx[4] = {-INFINITY, -INFINITY, -INFINITY, -INFINITY}, ls[4] = {0.f, 0.f, 0.f, 0.f};
+        if (act) {
+            const int ma = min(m0 + col, M - 1), ja = ma / R, ra = ma - ja * R;   // the A fragment's row
+            const bf16* qr = q + ((size_t)(kvh * R + ra) * rows + rs0 + ja) * hdp + quad * 8;
+            bf16x8 qa[HD / 32];
+#pragma unroll
+            for (int kk = 0; kk < HD / 32; ++kk) qa[kk] = *(const bf16x8*)(qr + kk * 32);
+            f32x4 sc[CH / 16];
+#pragma unroll
+            for (int nk = 0; nk < CH / 16; ++nk) {
+                sc[nk] = f32x4{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+                for (int kk = 0; kk < HD / 32; ++kk) {
+                    const bf16x8 kf = *(const bf16x8*)&k_s[nk * 16 + col][kk * 32 + quad * 8];
+                    sc[nk] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(qa[kk], kf, sc[nk], 0, 0, 0);
+                }
+            }
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {   // D: key nk * 16 + col, row quad * 4 + r; 16 lanes share a row
+                float m = -INFINITY;
+#pragma unroll
+                for (int nk = 0; nk < CH / 16; ++nk) {
+                    const float s = rv[r] && j0 + nk * 16 + col <= pos[r] ? sc[nk][r] * scale : -INFINITY;
+                    sc[nk][r] = s;
+                    m = fmaxf(m, s);
+                }
+#pragma unroll
+                for (int o = 8; o > 0; o >>= 1) m = fmaxf(m, __shfl_xor(m, o, 64));
+                float l = 0.f;
+#pragma unroll
+                for (int nk = 0; nk < CH / 16; ++nk) {
+                    const bf16 pb = (bf16)(m == -INFINITY ? 0.f : __expf(sc[nk][r] - m));
+                    l += (float)pb;
+                    p_s[w][quad * 4 + r][nk * 16 + col] = pb;
+                }
+#pragma unroll
+                for (int o = 8; o > 0; o >>= 1) l += __shfl_xor(l, o, 64);
+                mx[r] = m;
+                ls[r] = l;
+            }
+        }
+        __syncthreads();   // p_s[w]: written in the D layout, read back as A fragments
+        if (!have) continue;
+        f32x4 oacc[HD / 16];
+#pragma unroll
+        for (int nd = 0; nd < HD / 16; ++nd) oacc[nd] = f32x4{0.f, 0.f, 0.f, 0.f};
+        if (act) {
+#pragma unroll
+            for (int kk = 0; kk < CH / 32; ++kk) {
+                const bf16x8 pa = *(const bf16x8*)&p_s[w][col][kk * 32 + quad * 8];
+#pragma unroll
+                for (int nd = 0; nd < HD / 16; ++nd) {
+                    const bf16x8 vf = *(const bf16x8*)&vt_s[nd * 16 + col][kk * 32 + quad * 8];
+                    oacc[nd] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(pa, vf, oacc[nd], 0, 0, 0);
+                }
+            }
+        }
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+            if (!rv[r]) continue;
+            float* pp = part + poff[r];
+#pragma unroll
+            for (int nd = 0; nd < HD / 16; ++nd) pp[2 + nd * 16 + col] = oacc[nd][r];
+            if (col == 0) { pp[0] = mx[r]; pp[1] = ls[r]; }
+        }
+    }
+}
+
 }  // namespace
 
 // Launch plan of k_gemv_batch: a function of (N, K) alone.  Never of nb.
@@ -764,6 +1059,102 @@ int launch_attn_decode_batch(const void* q, const void* k_new, const void* v_new
     return KD_OK;
 }
 
+size_t gemv_rows_ws(int rows, int N, int K, int epi) {
+    if (rows < 1 || N <= 0 || K <= 0) return 0;
+    const GemvBatchPlan p = gemv_batch_plan(N, K);
+    if (p.ksplit == 1) return 0;
+    const int rows16 = p.wave_n ? GB_ROWS : (rows + GB_ROWS - 1) / GB_ROWS * GB_ROWS;   // wave_n = 1: one slab at a time
+    return (size_t)p.ksplit * (epi == 3 ? 2 : 1) * rows16 * N * sizeof(float);
+}
+
+int launch_gemv_rows(const void* x, int64_t ldx, int rows, const void* W, int64_t ldw, const void* extra, void* y, int N,
+                     int K, int epi, int I, const void* norm_w, float eps, void* ws, size_t ws_bytes, void* stream) {
+    KD_CHECK_ARG(x && W && y, "gemv_rows: null pointer");
+    KD_CHECK_ARG(epi >= 0 && epi <= 3 && (epi == 0 || epi == 3 || extra), "gemv_rows: epilogue 0..3 (1, 2 need extra)");
+    KD_CHECK_SHAPE(rows >= 1 && rows <= KD_GEMV_ROWS_MAX, "gemv_rows: 1 <= rows <= KD_GEMV_ROWS_MAX");
+    KD_CHECK_SHAPE(N > 0 && K > 0 && K % 8 == 0 && K <= 16384 && ldw >= K && ldw % 8 == 0 && ldx >= K && ldx % 8 == 0,
+                   "gemv_rows: K must be a multiple of 8 (<= 16384), ldw and ldx >= K and multiples of 8");
+    KD_CHECK_SHAPE(epi != 3 || I >= N, "gemv_rows: SwiGLU needs inter >= N");
+    KD_CHECK_ALIGN(W, 16, "gemv_rows: W misaligned");
+    KD_CHECK_ALIGN(x, 16, "gemv_rows: x misaligned");
+    KD_CHECK_ALIGN(norm_w, 16, "gemv_rows: norm_w misaligned");
+    const GemvBatchPlan p = gemv_batch_plan(N, K);
+    if (p.ksplit > 1 && (!ws || ws_bytes < gemv_rows_ws(rows, N, K, epi)))
+        return fail(KD_ERR_WORKSPACE, "gemv_rows: workspace too small (kd_gemv_rows_workspace_size)");
+    const bf16 *xb = (const bf16*)x, *Wb = (const bf16*)W, *eb = (const bf16*)extra, *nw = (const bf16*)norm_w;
+    if (p.wave_n) {
+        // one tile per wave (the lm_head): a wave's share of the weights does not fit its registers,
+        // so these plans make one kd_gemv_batch pass per slab (generation gives them <= 16 rows)
+        for (int row0 = 0; row0 < rows; row0 += GB_ROWS) {
+            const int rc = launch_gemv_batch(xb + (size_t)row0 * ldx, ldx, std::min(GB_ROWS, rows - row0), W, ldw,
+                                             epi == 2 ? (const void*)(eb + (size_t)row0 * N) : extra,
+                                             (bf16*)y + (size_t)row0 * N, N, K, epi, I, norm_w, eps, ws, ws_bytes, stream);
+            if (rc != KD_OK) return rc;
+        }
+        return KD_OK;
+    }
+    const int rows16 = (rows + GB_ROWS - 1) / GB_ROWS * GB_ROWS;
+    const dim3 grid(p.wg_n, p.ksplit, std::min(rows16 / GB_ROWS, GS_SLAB_GROUPS)), rgrid((N + NT - 1) / NT, rows);
+    const size_t lds = (size_t)GB_ROWS * (p.slice_steps * 32 + GB_PAD) * sizeof(bf16);
+    hipStream_t s = as_stream(stream);
+#define KD_GS(E)                                                                                                       \
+    do {                                                                                                               \
+        hipLaunchKernelGGL(k_gemv_slabs<E>, grid, dim3(NT), lds, s, xb, ldx, Wb, ldw, eb, (bf16*)y, (float*)ws, rows,  \
+                           N, K, I, nw, eps, p.slice_steps, p.ksplit);                                                 \
+        if (p.ksplit > 1)                                                                                              \
+            hipLaunchKernelGGL(k_gemv_slabs_reduce<E>, rgrid, dim3(NT), 0, s, (const float*)ws, eb, (bf16*)y, rows,    \
+                               rows16, N, p.ksplit);                                                                   \
+    } while (0)
+    switch (epi) {
+        case 0: KD_GS(0); break;
+        case 1: KD_GS(1); break;
+        case 2: KD_GS(2); break;
+        default: KD_GS(3);
+    }
+#undef KD_GS
+    KD_LAUNCH_CHECK("k_gemv_slabs");
+    return KD_OK;
+}
+
+size_t attn_extend_ws(int rows, int H, int hd, int smax) {
+    return (size_t)std::max(rows, 0) * attn_decode_ws(H, hd, smax);
+}
+
+int launch_attn_extend(const void* q, const void* k_new, const void* v_new, void* kc, void* vc, void* o, int nb,
+                       int rows, int H, int HKV, int hd, int hdp, int smax, const int* row_start, const int* base,
+                       void* ws, size_t ws_bytes, void* stream) {
+    KD_CHECK_ARG(q && k_new && v_new && kc && vc && o && row_start && base && ws, "attn_extend: null pointer");
+    KD_CHECK_SHAPE(rows >= 1 && rows <= KD_GEMV_ROWS_MAX && nb >= 1 && nb <= rows,
+                   "attn_extend: 1 <= nb <= rows <= KD_GEMV_ROWS_MAX");
+    KD_CHECK_SHAPE(hd == 64 || hd == 128, "attn_extend: head dim must be 64 or 128");
+    KD_CHECK_SHAPE(hdp >= hd && hdp % 8 == 0, "attn_extend: hdp must be >= hd and a multiple of 8");
+    KD_CHECK_SHAPE(H > 0 && HKV > 0 && H % HKV == 0, "attn_extend: heads must be a multiple of kv heads");
+    KD_CHECK_SHAPE(smax > 0 && smax <= MAX_CH * CH, "attn_extend: need 0 < smax <= 32768");
+    KD_CHECK_ALIGN(q, 16, "attn_extend: q misaligned");
+    KD_CHECK_ALIGN(kc, 16, "attn_extend: k cache misaligned");
+    KD_CHECK_ALIGN(vc, 16, "attn_extend: v cache misaligned");
+    KD_CHECK_ALIGN(k_new, 16, "attn_extend: k_new misaligned");
+    KD_CHECK_ALIGN(v_new, 16, "attn_extend: v_new misaligned");
+    if (ws_bytes < attn_extend_ws(rows, H, hd, smax)) return fail(KD_ERR_WORKSPACE, "attn_extend: workspace too small");
+    const int nch = (smax + CH - 1) / CH;
+    const float scale = 1.0f / sqrtf((float)hd);
+    hipStream_t s = as_stream(stream);
+    float* part = (float*)ws;
+    if (hd == 64) {
+        hipLaunchKernelGGL(k_attn_extend_part<64>, dim3(HKV, nch, nb), dim3(NT), 0, s, (const bf16*)q,
+                           (const bf16*)k_new, (const bf16*)v_new, (bf16*)kc, (bf16*)vc, part, H, HKV, hdp, smax, rows,
+                           row_start, base, scale);
+        hipLaunchKernelGGL(k_attn_decode_combine<64>, dim3(rows * H), dim3(NT), 0, s, part, nch, (bf16*)o);
+    } else {
+        hipLaunchKernelGGL(k_attn_extend_part<128>, dim3(HKV, nch, nb), dim3(NT), 0, s, (const bf16*)q,
+                           (const bf16*)k_new, (const bf16*)v_new, (bf16*)kc, (bf16*)vc, part, H, HKV, hdp, smax, rows,
+                           row_start, base, scale);
+        hipLaunchKernelGGL(k_attn_decode_combine<128>, dim3(rows * H), dim3(NT), 0, s, part, nch, (bf16*)o);
+    }
+    KD_LAUNCH_CHECK("k_attn_extend");
+    return KD_OK;
+}
+
 int launch_gen_select_batch(const void* logits, int64_t ldl, int V, int64_t* seq, int smax, int nb, int* cur_dev,
                             float penalty, int ngram, void* flags_ws, size_t ws_bytes, int64_t* out, void* stream) {
     KD_CHECK_ARG(logits && seq && cur_dev && flags_ws, "gen_select_batch: null pointer");
@@ -780,7 +1171,8 @@ int launch_gen_select_batch(const void* logits, int64_t ldl, int V, int64_t* seq
 int launch_rope_rows(const float* cos_t, const float* sin_t, int hh, int rows, int nb, const int* cur_dev,
                      float* cos_rows, float* sin_rows, void* stream) {
     KD_CHECK_ARG(cos_t && sin_t && cur_dev && cos_rows && sin_rows, "rope_rows: null pointer");
-    KD_CHECK_SHAPE(hh > 0 && rows > 0 && nb >= 1 && nb <= GB_ROWS, "rope_rows: hh, rows positive, 1 <= nb <= 16");
+    KD_CHECK_SHAPE(hh > 0 && rows > 0 && nb >= 1 && nb <= KD_GEMV_ROWS_MAX,
+                   "rope_rows: hh, rows positive, 1 <= nb <= KD_GEMV_ROWS_MAX");
     hipLaunchKernelGGL(k_rope_rows, dim3(nb), dim3(256), 0, as_stream(stream), cos_t, sin_t, hh, rows, cur_dev, cos_rows,
                        sin_rows);
     KD_LAUNCH_CHECK("k_rope_rows");

@@ -78,6 +78,13 @@ int launch_gen_select_batch(const void* logits, int64_t ldl, int V, int64_t* seq
                             float penalty, int ngram, void* flags_ws, size_t ws_bytes, int64_t* out, void* stream);
 int launch_rope_rows(const float* cos_t, const float* sin_t, int hh, int rows, int nb, const int* cur_dev,
                      float* cos_rows, float* sin_rows, void* stream);
+size_t gemv_rows_ws(int rows, int N, int K, int epi);
+int launch_gemv_rows(const void* x, int64_t ldx, int rows, const void* W, int64_t ldw, const void* extra, void* y, int N,
+                     int K, int epi, int I, const void* norm_w, float eps, void* ws, size_t ws_bytes, void* stream);
+size_t attn_extend_ws(int rows, int H, int hd, int smax);
+int launch_attn_extend(const void* q, const void* k_new, const void* v_new, void* kc, void* vc, void* o, int nb,
+                       int rows, int H, int HKV, int hd, int hdp, int smax, const int* row_start, const int* base,
+                       void* ws, size_t ws_bytes, void* stream);
 int launch_image_resize(const uint8_t* in, int H, int W, uint8_t* out, int oh, int ow, void* ws, size_t ws_bytes,
                         void* stream);
 int launch_anyres_tiles(const uint8_t* base, const uint8_t* resized, int nh, int nw, int bh, int bw, int patch,

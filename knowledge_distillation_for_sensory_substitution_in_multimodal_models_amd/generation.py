@@ -20,12 +20,23 @@ transformers' generate (B = 1, as the evaluation runs it).
 generate_batch() decodes up to 16 such prompts per step (ragged lengths, per-row device counters,
 batch-invariant kernels): the evaluation's one-question-at-a-time loop with the weights streamed
 once per step for all rows.
+
+generate_grouped() takes the questions grouped by image, as the evaluation's prompts are laid out
+(image first, then the question): the SigLIP tower, the projector and every layer's K/V up to the
+last image token depend on the image alone, so that prefix is prefilled once per image and copied
+into the cache of each of its questions; the ragged question suffixes of a chunk then run through
+the layers together (kd_gemv_rows: the decode GEMV for more than 16 rows without reading the
+weights again per 16 rows; kd_attn_extend: suffix queries against prefix + own suffix) and the
+batched decode of generate_batch() takes over.  A question's result depends on its image, the
+shared prefix and its own suffix only (bit for bit); it is held to generate_batch()'s oracle
+bounds but is not bit-identical to generate_batch() on the same prompt.
 """
 from __future__ import annotations
 
 import torch
 
 from . import ops
+from ._native import KD_GEMV_ROWS_MAX
 
 
 EOS_TOKEN_IDS = (151645,)   # <|im_end|>: generation_config.eos_token_id of the -ov-hf chat checkpoints
@@ -182,15 +193,13 @@ def generate_batch(model, prompts, max_new_tokens: int = 32, repetition_penalty:
 
 def _generate_rows(model, prompts, max_new_tokens, repetition_penalty, no_repeat_ngram_size, eos_token_id,
                    return_logits, graph):
-    T, P = model.cfg.text, model.P
+    T = model.cfg.text
     dev = model.device
     nb = len(prompts)
     Ls = [int(ids.shape[1]) for ids, _, _ in prompts]
     smax = max(Ls) + max_new_tokens
     eos = {int(e) for e in ([eos_token_id] if isinstance(eos_token_id, int) else (eos_token_id or ()))}
-    nq, nkv, hd = T.heads, T.kv_heads, T.head_dim
-    qd, kd = nq * hd, nkv * hd
-    lp = "language_model.model."
+    nkv, hd = T.kv_heads, T.head_dim
 
     # ---- prefill, one prompt at a time: generate()'s own (row b of the caches and of seq)
     kc = torch.empty((T.layers, nb, nkv, smax, hd), dtype=torch.bfloat16, device=dev)
@@ -212,9 +221,15 @@ def _generate_rows(model, prompts, max_new_tokens, repetition_penalty, no_repeat
             steps[b].append(logits)
         ops.gen_select(logits, seq[b], L, repetition_penalty, no_repeat_ngram_size)
 
-    cos, sin = model._rope_for(smax)
-    src = torch.full((nb,), -2, dtype=torch.int32, device=dev)   # token embedding (kd_embed_assemble)
-    table = P[lp + "embed_tokens.weight"]
+    return _decode_rows(model, kc, vc, seq, Ls, steps, max_new_tokens, repetition_penalty, no_repeat_ngram_size, eos,
+                        return_logits, graph)
+
+
+def _decode_layers(model):
+    """Per layer: (input norm, q|k|v weight, q|k|v bias, o_proj, post-attention norm, gate|up, down)."""
+    T, P = model.cfg.text, model.P
+    qd, kd = T.heads * T.head_dim, T.kv_heads * T.head_dim
+    lp = "language_model.model."
     layers = []
     for i in range(T.layers):
         p = f"{lp}layers.{i}."
@@ -224,6 +239,22 @@ def _generate_rows(model, prompts, max_new_tokens, repetition_penalty, no_repeat
                        P[p + "self_attn.o_proj.weight"], P[p + "post_attention_layernorm.weight"],
                        P.span(p + "mlp.gate_proj.weight", p + "mlp.up_proj.weight", 2 * T.inter, T.hidden),
                        P[p + "mlp.down_proj.weight"]))
+    return layers
+
+
+def _decode_rows(model, kc, vc, seq, Ls, steps, max_new_tokens, repetition_penalty, no_repeat_ngram_size, eos,
+                 return_logits, graph):
+    """The batched decode loop behind generate_batch() and generate_grouped(): row b's caches hold
+    its L_b prompt positions, seq[b, L_b] its first new token and steps[b] that token's logits row."""
+    T, P = model.cfg.text, model.P
+    dev = model.device
+    nb, smax = seq.shape
+    nq, nkv, hd = T.heads, T.kv_heads, T.head_dim
+    lp = "language_model.model."
+    cos, sin = model._rope_for(smax)
+    src = torch.full((nb,), -2, dtype=torch.int32, device=dev)   # token embedding (kd_embed_assemble)
+    table = P[lp + "embed_tokens.weight"]
+    layers = _decode_layers(model)
     # device-resident per-row step state (generate()'s, one entry per row)
     cur = torch.tensor([L + 1 for L in Ls], dtype=torch.int32, device=dev)
     tok = torch.stack([seq[b, Ls[b]] for b in range(nb)])   # the tokens being decoded
@@ -271,3 +302,135 @@ def _generate_rows(model, prompts, max_new_tokens, repetition_penalty, no_repeat
             steps[b] = steps[b][:ends[b] - L]
     outs = [seq[b, :ends[b]].view(1, ends[b]) for b in range(nb)]
     return outs, (steps if return_logits else [])
+
+
+@torch.no_grad()
+def generate_grouped(model, groups, max_new_tokens: int = 32, repetition_penalty: float = 1.0,
+                     no_repeat_ngram_size: int = 0, eos_token_id=EOS_TOKEN_IDS, pad_token_id: int | None = None,
+                     temperature: float | None = None, return_logits: bool = False, graph: bool = True):
+    """generate_batch() for questions grouped by image: groups is a sequence of (pixel_values
+    [1, P, 3, 384, 384], image_sizes [1, 2], [input_ids [1, L_q], ...]) -> one list per group of int64
+    [1, L_q + n_q] (and, with return_logits, the same nesting of per-step bf16 logits rows).
+
+    P0 is the index of the group's last image token plus one.  Every question of a group must
+    agree on ids[:P0] and have at least one token after it (ValueError otherwise).  The prefix
+    ids[:P0] (template head + image) runs once per group through the training forward and seeds
+    the cache of each of its questions; the suffixes ids[P0:] of up to MAX_BATCH questions then run
+    through the layers together as ragged rows on the decode kernels' route (kd_gemv_rows,
+    kd_attn_extend), and the batched decode of generate_batch() produces the remaining tokens.
+    P0 is set by the image tokens, not by what the questions happen to share, so a question's
+    tokens and logits depend only on its image, ids[:P0] and its own suffix, bit for bit: not on the
+    other questions of its group, on other groups, on the chunk or on its slot.
+
+    Not bit-identical to generate_batch() on the same prompt (the prefix forward runs at M = P0
+    instead of M = L and the suffix rows take the decode kernels); both are held to the same bounds
+    against the oracle."""
+    del temperature, pad_token_id   # greedy; finished rows are cut, not padded
+    groups = [(px, sizes, list(qs)) for px, sizes, qs in groups]
+    if not groups:
+        raise ValueError("generate_grouped: no groups")
+    if int(max_new_tokens) < 1:
+        raise ValueError("generate_grouped: max_new_tokens must be >= 1")
+    image_token = int(model.cfg.image_token_id)
+    items = []   # (group, pixel_values, image_sizes, input_ids, P0), flattened in order
+    for gi, (px, sizes, qs) in enumerate(groups):
+        if not qs:
+            raise ValueError(f"generate_grouped: group {gi} has no question")
+        head, P0 = None, 0
+        for ids in qs:
+            if ids.dim() != 2 or ids.shape[0] != 1:
+                raise ValueError("generate_grouped: every question's input_ids must be [1, L]")
+            host = ids[0].tolist()
+            last = max((i for i, t in enumerate(host) if t == image_token), default=-1)
+            if last < 0:
+                raise ValueError(f"generate_grouped: a question of group {gi} has no image token")
+            if head is None:
+                head, P0 = host[:last + 1], last + 1
+            elif last + 1 != P0 or host[:P0] != head:
+                raise ValueError(f"generate_grouped: the questions of group {gi} differ up to the last image token")
+            if len(host) <= P0:
+                raise ValueError(f"generate_grouped: a question of group {gi} ends on an image token")
+            if len(host) - P0 > KD_GEMV_ROWS_MAX:
+                raise ValueError(f"generate_grouped: more than {KD_GEMV_ROWS_MAX} tokens after the image")
+            items.append((gi, px, sizes, ids, P0))
+    outs, logs = [[] for _ in groups], [[] for _ in groups]
+    carry = (None, None)   # the prefix K/V of the group a chunk ended in: its next chunk reuses them
+    for c0 in range(0, len(items), MAX_BATCH):
+        chunk = items[c0:c0 + MAX_BATCH]
+        o, lg, carry = _generate_grouped_rows(model, chunk, carry, int(max_new_tokens), repetition_penalty,
+                                              no_repeat_ngram_size, eos_token_id, return_logits, graph)
+        for (gi, *_), ob, lb in zip(chunk, o, lg if return_logits else [None] * len(o)):
+            outs[gi].append(ob)
+            logs[gi].append(lb)
+    return (outs, logs) if return_logits else outs
+
+
+def _generate_grouped_rows(model, chunk, carry, max_new_tokens, repetition_penalty, no_repeat_ngram_size, eos_token_id,
+                           return_logits, graph):
+    T, P = model.cfg.text, model.P
+    dev = model.device
+    nb = len(chunk)
+    Ls = [int(ids.shape[1]) for _, _, _, ids, _ in chunk]
+    P0s = [P0 for *_, P0 in chunk]
+    smax = max(Ls) + max_new_tokens
+    eos = {int(e) for e in ([eos_token_id] if isinstance(eos_token_id, int) else (eos_token_id or ()))}
+    nq, nkv, hd = T.heads, T.kv_heads, T.head_dim
+    lp = "language_model.model."
+
+    kc = torch.empty((T.layers, nb, nkv, smax, hd), dtype=torch.bfloat16, device=dev)
+    vc = torch.empty_like(kc)
+    seq = torch.zeros((nb, smax), dtype=torch.int64, device=dev)
+    # ---- prefix prefill, once per group: the training forward over ids[:P0], copied into every slot of the group
+    for b, (gi, px, sizes, ids, P0) in enumerate(chunk):
+        if carry[0] != gi:
+            kv = []
+            model.forward(ids[:, :P0], px, sizes, save=False, kv_out=kv)
+            carry = (gi, kv)
+        for i, (k, v) in enumerate(carry[1]):
+            kc[i, b, :, :P0].copy_(k[0])
+            vc[i, b, :, :P0].copy_(v[0])
+        seq[b, :Ls[b]].copy_(ids[0])
+
+    # ---- extend pass: every suffix row of the chunk through the layers at once (sub-ranges of
+    # questions only if the rows exceed the kernels' cap; a question's bits do not depend on the split)
+    cos, sin = model._rope_for(smax)
+    table = P[lp + "embed_tokens.weight"]
+    layers = _decode_layers(model)
+    last = []
+    b0 = 0
+    while b0 < nb:
+        b1, R = b0, 0
+        while b1 < nb and R + Ls[b1] - P0s[b1] <= KD_GEMV_ROWS_MAX:
+            R += Ls[b1] - P0s[b1]
+            b1 += 1
+        starts = [0]
+        for b in range(b0, b1):
+            starts.append(starts[-1] + Ls[b] - P0s[b])
+        row_start = torch.tensor(starts, dtype=torch.int32, device=dev)
+        base = torch.tensor(P0s[b0:b1], dtype=torch.int32, device=dev)
+        cur_rows = torch.tensor([P0s[b] + j + 1 for b in range(b0, b1) for j in range(Ls[b] - P0s[b])],
+                                dtype=torch.int32, device=dev)   # position + 1, as the decode step's counter
+        toks = torch.cat([chunk[b][3][0, P0s[b]:] for b in range(b0, b1)]).contiguous()
+        src = torch.full((R,), -2, dtype=torch.int32, device=dev)   # token embedding (kd_embed_assemble)
+        cos_rows = torch.empty((R, cos.shape[1]), dtype=torch.float32, device=dev)
+        sin_rows = torch.empty_like(cos_rows)
+        ops.rope_rows(cos, sin, cur_rows, cos_rows, sin_rows)
+        x = ops.embed_assemble(toks, src, table, None, None, model.err)
+        for i, (w_in, Wqkv, bqkv, Wo, w_post, Wgu, Wdown) in enumerate(layers):
+            qkv = ops.gemv_rows(x, Wqkv, bias=bqkv, norm_w=w_in, eps=T.eps)      # input_layernorm fused
+            q, k, v = ops.qkv_split(qkv, 1, R, nq, nkv, hd, hd, cos_rows, sin_rows)   # row r rotated by its position
+            o = ops.attn_extend(q[0], k[0], v[0], kc[i, b0:b1], vc[i, b0:b1], row_start, base, hd)
+            x_mid = ops.gemv_rows(o, Wo, residual=x)
+            a = ops.gemv_rows(x_mid, Wgu, swiglu_inter=T.inter, norm_w=w_post, eps=T.eps)  # post_attention_layernorm
+            x = ops.gemv_rows(a, Wdown, residual=x_mid)
+        last.append(x.index_select(0, (row_start[1:] - 1).long()))   # each question's last suffix row
+        b0 = b1
+    xl = last[0] if len(last) == 1 else torch.cat(last)
+    hn, _, _ = ops.norm_fwd(xl, P[lp + "norm.weight"], None, T.eps, rms=True, save_stats=False)
+    lg = ops.gemv_batch(hn, model.lm_head_weight())
+    cur = torch.tensor(Ls, dtype=torch.int32, device=dev)
+    ops.gen_select_batch(lg, seq, cur, repetition_penalty, no_repeat_ngram_size)   # seq[b, L_b]; cur = L_b + 1
+    steps = [[lg[b:b + 1]] if return_logits else [] for b in range(nb)]
+    outs, steps = _decode_rows(model, kc, vc, seq, Ls, steps, max_new_tokens, repetition_penalty,
+                               no_repeat_ngram_size, eos, return_logits, graph)
+    return outs, steps, carry

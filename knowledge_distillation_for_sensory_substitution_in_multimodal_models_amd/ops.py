@@ -858,3 +858,66 @@ def gen_select_batch(logits: torch.Tensor, seq: torch.Tensor, cur: torch.Tensor,
     NV.call("kd_gen_select_batch", logits.data_ptr(), max(logits.stride(0), V), V, seq.data_ptr(), seq.shape[1], nb,
             cur.data_ptr(), float(repetition_penalty), int(no_repeat_ngram_size), ws.data_ptr(), ws.numel(), _ptr(out),
             _stream())
+
+
+# ------------------------------------------------------------ grouped prefill ----
+def gemv_rows(x: torch.Tensor, w: torch.Tensor, *, bias=None, residual=None, swiglu_inter: int = 0, norm_w=None,
+              eps: float = 1e-6, out: torch.Tensor | None = None) -> torch.Tensor:
+    """gemv_batch() for 1 <= rows <= KD_GEMV_ROWS_MAX rows, the weights kept in registers across the
+    16-row slabs instead of read again per slab (kd_gemv_rows): x [rows, K] bf16, w [N, K] ->
+    [rows, N] bf16, same epilogues and fused RMSNorm.  Row r of the result is bit-identical to gemv_batch() on row r alone."""
+    _require(x, torch.bfloat16, "gemv_rows.x")
+    if x.dim() != 2 or x.stride(1) != 1:
+        raise RuntimeError("gemv_rows: x must be [rows, K] with a contiguous last dim")
+    rows, K = x.shape
+    epi, extra = 0, None
+    if swiglu_inter:
+        epi, N = 3, int(swiglu_inter)
+    else:
+        N = w.shape[0]
+        if bias is not None:
+            epi, extra = 1, bias
+        elif residual is not None:
+            epi, extra = 2, residual
+            if residual.shape != (rows, N) or not residual.is_contiguous():
+                raise RuntimeError("gemv_rows: residual must be a contiguous [rows, N] tensor")
+    if out is None:
+        out = torch.empty((rows, N), dtype=torch.bfloat16, device=x.device)
+    elif out.shape != (rows, N) or out.dtype != torch.bfloat16 or not out.is_contiguous():
+        raise RuntimeError("gemv_rows: out must be a contiguous bf16 [rows, N] tensor")
+    nbytes = NV.lib().kd_gemv_rows_workspace_size(rows, N, K, epi)
+    ws = _workspace(("gemv_rows", _stream()), nbytes, x.device) if nbytes else None
+    NV.call("kd_gemv_rows", x.data_ptr(), max(x.stride(0), K), rows, w.data_ptr(), w.stride(0), _ptr(extra),
+            out.data_ptr(), N, K, epi, int(swiglu_inter), _ptr(norm_w), float(eps), _ptr(ws),
+            0 if ws is None else ws.numel(), _stream())
+    return out
+
+
+def attn_extend(q: torch.Tensor, k_new: torch.Tensor, v_new: torch.Tensor, k_cache: torch.Tensor,
+                v_cache: torch.Tensor, row_start: torch.Tensor, base: torch.Tensor, hd: int,
+                out: torch.Tensor | None = None) -> torch.Tensor:
+    """Ragged suffix rows against their question's cache prefix and own suffix (kd_attn_extend).
+    q [H, rows, hdp], k_new/v_new [HKV, rows, hdp] (qkv_split(B=1, S=rows)), caches
+    [nb, HKV, smax, hdp], row_start [nb + 1] and base [nb] int32 on the device -> o [rows, H*hd]
+    bf16.  Question b's row j (row row_start[b] + j) sits at position base[b] + j and sees positions
+    [0, base[b] + j]; its k_new/v_new rows are stored at [base[b], base[b] + S_b)."""
+    H, rows, hdp = q.shape
+    nb, HKV, smax, _ = k_cache.shape
+    _require(row_start, torch.int32, "attn_extend.row_start")
+    _require(base, torch.int32, "attn_extend.base")
+    if row_start.numel() != nb + 1 or base.numel() != nb or k_new.shape != (HKV, rows, hdp) or v_new.shape != k_new.shape \
+            or v_cache.shape != k_cache.shape:
+        raise RuntimeError("attn_extend: q [H, rows, hdp], k_new/v_new [HKV, rows, hdp], caches [nb, HKV, smax, hdp], "
+                           "row_start [nb + 1], base [nb]")
+    for t, n in ((q, "q"), (k_new, "k_new"), (v_new, "v_new"), (k_cache, "k_cache"), (v_cache, "v_cache")):
+        _require(t, torch.bfloat16, f"attn_extend.{n}")
+        if not t.is_contiguous():
+            raise RuntimeError(f"attn_extend: {n} must be contiguous")
+    if out is None:
+        out = torch.empty((rows, H * hd), dtype=torch.bfloat16, device=q.device)
+    nbytes = NV.lib().kd_attn_extend_workspace_size(rows, H, hd, smax)
+    ws = _workspace(("attn_extend", _stream()), nbytes, q.device)
+    NV.call("kd_attn_extend", q.data_ptr(), k_new.data_ptr(), v_new.data_ptr(), k_cache.data_ptr(),
+            v_cache.data_ptr(), out.data_ptr(), nb, rows, H, HKV, hd, hdp, smax, row_start.data_ptr(),
+            base.data_ptr(), ws.data_ptr(), ws.numel(), _stream())
+    return out

@@ -3,7 +3,10 @@ prefill of one 336x336 prompt (L = 1536) + 32 greedy decode steps with the KV ca
     python tools/bench_generate.py
     python tools/bench_generate.py --batch 16    also generate_batch() at nb in {1, 2, 4, 8, 16} <= 16:
                                                  the batched step against the single-prompt step
-                                                 measured in the same process"""
+                                                 measured in the same process
+    python tools/bench_generate.py --grouped 6   also generate_grouped(): 16 prompts over ceil(16 / 6) images
+                                                 (6 questions per image) against generate_batch() on the same
+                                                 16 prompts, same process; --grouped 1: nothing is shared"""
 import argparse
 import sys
 import time
@@ -14,13 +17,15 @@ import torch
 sys.path.insert(0, str(Path(__file__).resolve().parent.parent))
 from knowledge_distillation_for_sensory_substitution_in_multimodal_models_amd.data import synthetic_batch  # noqa
 from knowledge_distillation_for_sensory_substitution_in_multimodal_models_amd.generation import (  # noqa
-    generate, generate_batch)
+    generate, generate_batch, generate_grouped)
 from knowledge_distillation_for_sensory_substitution_in_multimodal_models_amd.modeling import (  # noqa
     STUDENT_05B, LlavaOnevisionModel)
 
 ap = argparse.ArgumentParser()
 ap.add_argument("--batch", type=int, default=0, metavar="N",
                 help="also time generate_batch() at every nb in {1, 2, 4, 8, 16} up to N")
+ap.add_argument("--grouped", type=int, default=0, metavar="Q",
+                help="also time generate_grouped() on 16 prompts, Q questions per image, against generate_batch()")
 args = ap.parse_args()
 
 dev = torch.device("cuda:0")
@@ -70,3 +75,29 @@ if args.batch > 0:
         print(f"  nb={nb:2d}: {tb[0] * 1e3:7.1f} ms per call of 32 tokens; decode step {step:.3f} ms/step = "
               f"{step / nb:.3f} ms/token/row ({step / step1:.2f}x the single-prompt step, "
               f"{step1 * nb / step:.2f}x its tokens/s)")
+
+if args.grouped > 0:
+    # 16 prompts over ceil(16 / Q) synthetic 336x336 images, L = 1536 each: one synthetic_batch per image
+    # (template head + image tokens), the 27 ids after the last image token redrawn per question
+    from knowledge_distillation_for_sensory_substitution_in_multimodal_models_amd.data import TEXT_VOCAB  # noqa
+    from knowledge_distillation_for_sensory_substitution_in_multimodal_models_amd.modeling import IMAGE_TOKEN_ID  # noqa
+    Q, NP = args.grouped, 16
+    groups, prompts = [], []
+    for g0 in range(0, NP, Q):
+        r = synthetic_batch(1, dev, L=1536, seed=100 + g0)
+        ids = r["depth_input_ids"]
+        P0 = int((ids[0] == IMAGE_TOKEN_ID).nonzero().max()) + 1
+        qs = []
+        for qi in range(g0, min(g0 + Q, NP)):
+            gq = torch.Generator().manual_seed(1000 + qi)
+            suf = torch.randint(0, TEXT_VOCAB, (1, 1536 - P0), generator=gq, dtype=torch.int64).to(dev)
+            qs.append(torch.cat([ids[:, :P0], suf], 1))
+        groups.append((r["depth_pixel_values"], r["image_sizes"], qs))
+        prompts += [(q, r["depth_pixel_values"], r["image_sizes"]) for q in qs]
+    print(f"generate_grouped, Q = {Q}: {NP} prompts over {len(groups)} images (L = 1536, {1536 - P0} tokens after "
+          f"the image), against generate_batch on the same prompts, same process")
+    for n in (32, 96):
+        tg = best_of(lambda: generate_grouped(model, groups, max_new_tokens=n, **kw))
+        tb = best_of(lambda: generate_batch(model, prompts, max_new_tokens=n, **kw))
+        print(f"  {n:2d} new tokens: generate_grouped {tg * 1e3:7.1f} ms per call, generate_batch {tb * 1e3:7.1f} ms "
+              f"per call, ratio {tg / tb:.3f} ({tb / tg:.2f}x)")
