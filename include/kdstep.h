@@ -483,6 +483,8 @@ int kd_rope_row(const float* cos_table, const float* sin_table, int hh, const in
  *   position cur_dev[b] - 1 of its cache, no other cache element is written.
  * kd_gen_select_batch: kd_gen_select per row: logits [nb, V] (rows ld_logits apart), seq
  *   [nb, smax] int64; writes seq[b][cur_dev[b]], out[b] (optional) and cur_dev[b] += 1.
+ *   A full row (cur_dev[b] == smax) has no slot left: out[b] still receives the choice made over
+ *   its smax ids and cur_dev[b] becomes smax + 1, but no element of seq is written.
  *   workspace >= nb * V bytes.
  * kd_rope_rows: cos/sin row of position cur_dev[b] - 1 of the [table_rows, hh] tables into row b
  *   of [nb, hh] buffers: as kd_qkv_split's tables with (B = 1, S = nb) they rotate token b by its

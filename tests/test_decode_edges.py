@@ -1,0 +1,834 @@
+"""Value tests of the decode kernels at the places where such kernels go wrong: one key too few or
+too many, the token's own row taken from the wrong place, a lost tie, a tail or an unaligned row.
+
+A. kd_attn_decode / kd_attn_decode_batch / kd_attn_extend against an fp64 reference on *probe /
+   poison* inputs.  Per kv head a unit vector u; every query is randn with its u component
+   replaced by a*u (a = 16); every key is randn with its u component removed, so ordinary scores
+   are ~N(0, 1).  One *probe* key gamma*u with gamma = sqrt(hd) * (ln n + 0.5) / a scores
+   ln n + 0.5 and so holds about half of the softmax weight (asserted on the reference: inside
+   [0.25, 0.75] for every head when n > 1); its value row is 3 + arange(hd) / hd (+ kv head / 4, so
+   that at n = 1, where the scores do not matter, the kv heads still differ).  With at most 8
+   keys the ordinary ones are not numerous enough to balance the probe by themselves, so they are
+   built around the mean query of the group instead (score ~1.2 for every head).  *Poison* (key
+   4*gamma*u, value 1000) fills every cache row the kernel must not read: everything at or past n
+   (decode), everything at or past base (extend), which includes the stale row n - 1 / the rows
+   the suffix is stored to.  Everything is rounded to bf16 before the reference is taken.
+
+   Bounds.  decode and decode_batch keep P in fp32, only the bf16 store rounds (2^-9 relative):
+       |got - ref| <= 2^-8 |ref| + c * (softmax(s) @ |v|),   c = 1e-4
+   (an fp32 emulation of the kernel's order -- 64-key chunks, per-chunk max, combine -- stays
+   within 1.5e-6 of the fp64 reference in units of P|V|; __expf adds about |x| * 2^-23 relative).
+   extend rounds P to bf16 through LDS: tests/test_attention_gpu.py's forward bound,
+       |got - ref| <= 2e-2 rms(ref) + 2e-2 |ref| + 2^-8 (P|V|).
+   Largest (|err| - 2^-8 |ref|) / (P|V|) measured on an MI355X over the cases below (every test
+   prints its own figure before it asserts):
+       kd_attn_decode        probe cases -7.0e-6 (the error never leaves the bf16 rounding of the
+                             reference), score-range cases 3.1e-6                    bound 1e-4
+       kd_attn_decode_batch  probe cases -7.0e-6, score-range cases 5.3e-6           bound 1e-4
+       kd_attn_extend        1.6e-3 (hd 128, probe at 0 / base - 1), hd 64: 1.3e-3   bound 2^-8 =
+                             3.9e-3 from the P|V| term alone, plus 2e-2 rms(ref) + 2e-2 |ref|
+
+   The cache stores copy all hdp columns of k_new / v_new (k_attn_decode_part,
+   k_attn_decode_part_batch: `d < hdp`; k_attn_extend_part: hdp / 8 chunks of 8), the padding
+   included, as include/kdstep.h says ("stored into the caches"); the scores and P.V read the
+   first hd columns only.  kd_attn_extend's launcher accepts hdp > hd like the other two.
+
+   test_probe_poison_bounds_reject_mutations (CPU) is the test of these tests: for every decode
+   case the bf16-rounded fp32 chunked emulation is accepted and every listed mutation of the
+   reference is rejected by the bound in at least one probe run; the same for extend.  The
+   score-range cases (no probe) only have their emulation checked there.
+
+B. kd_gen_select / kd_gen_select_batch == oracle.generation.select on the bf16-rounded scores, at
+   the vector tails, unaligned rows, planted and processor-made ties, all -inf rows, sequence
+   lengths around ngram and past the 1024-thread trip, and a full row (cur == smax).
+
+C. kd_rope_row / kd_rope_rows copy exactly table row pos - 1 (clamped into the table for the
+   batched form) and write nothing outside their destination.
+
+"""
+import functools
+import math
+from importlib import import_module
+from types import SimpleNamespace
+
+import numpy as np
+import pytest
+import torch
+
+from oracle import generation as G
+from test_generate_grouped import QUESTIONS, SMAX
+
+PKG = "knowledge_distillation_for_sensory_substitution_in_multimodal_models_amd"
+BF = torch.bfloat16
+F64 = torch.float64
+
+A_Q = 16.0         # the u component of every query
+POISON_V = 1000.0  # value rows (and padding columns) that must never be read
+C_DEC = 1e-4       # decode bound: 2^-8 |ref| + C_DEC * P|V|
+WORST = {}         # kernel -> largest (|err| - 2^-8 |ref|) / P|V| seen in this run
+
+
+def _ops():
+    return import_module(f"{PKG}.ops")
+
+
+# ------------------------------------------------------------------ inputs and references ----
+
+@functools.lru_cache(maxsize=None)
+def _question(hd, H, HKV, base, S, probe, kind="probe"):
+    """One sequence of N = base + S keys with S query rows at positions base .. N - 1 (decode: S = 1,
+    base = n - 1).  bf16 tensors q [H, S, hd], K / V [HKV, N, hd], the poison key pk [HKV, hd]."""
+    N, R, sq = base + S, H // HKV, math.sqrt(hd)
+    g = torch.Generator().manual_seed((((hd + H) * 40009 + base) * 67 + S) * 11 + (probe if probe is not None else 7))
+    u = torch.randn(HKV, hd, generator=g, dtype=F64)
+    u = u / u.norm(dim=-1, keepdim=True)
+    uh, uk = u.repeat_interleave(R, 0)[:, None, :], u[:, None, :]
+    q = torch.randn(H, S, hd, generator=g, dtype=F64)
+    qperp = q - (q * uh).sum(-1, keepdim=True) * uh
+    q = qperp + A_Q * uh
+    K = torch.randn(HKV, N, hd, generator=g, dtype=F64)
+    K = K - (K * uk).sum(-1, keepdim=True) * uk
+    V = torch.randn(HKV, N, hd, generator=g, dtype=F64)
+    if kind == "probe":
+        gamma = sq * (math.log(N) + 0.5) / A_Q
+        if 1 < N <= 8:   # too few ordinary keys for their sum to be steady: score ~1.2 for every head of the group
+            m = qperp.reshape(HKV, R * S, hd).mean(1)
+            K = 0.1 * K + (1.2 * sq * m / (m * m).sum(-1, keepdim=True))[:, None, :]
+        K[:, probe] = gamma * u
+        V[:, probe] = 3 + torch.arange(hd, dtype=F64) / hd + torch.arange(HKV, dtype=F64)[:, None] / 4
+        pk = 4 * gamma * u
+    elif kind == "sink":   # position 0 scores +60, every other key about -40
+        K = K - (40 * sq / A_Q) * uk
+        K[:, 0] = (60 * sq / A_Q) * u
+        pk = (100 * sq / A_Q) * u
+    else:                  # "low": every score about -200
+        assert kind == "low"
+        K = K - (200 * sq / A_Q) * uk
+        pk = (100 * sq / A_Q) * u
+    return SimpleNamespace(hd=hd, H=H, HKV=HKV, base=base, S=S, N=N, probe=probe, kind=kind,
+                           q=q.to(BF), K=K.to(BF), V=V.to(BF), pk=pk.to(BF))
+
+
+def _causal(Q, extra=0):
+    return torch.arange(Q.N + extra)[None, :] <= (Q.base + torch.arange(Q.S))[:, None]   # [S, N]
+
+
+def _attend(q, K, V, mask, kv=None):
+    """fp64 attention: q [H, S, hd], K / V [HKV, Nk, hd], mask [S, Nk] (True = visible), kv the kv head
+    of every query head -> o, P|V| [S, H, hd], P [H, S, Nk].  A row that sees nothing gives zeros."""
+    q, K, V = q.double(), K.double(), V.double()
+    H, hd = q.shape[0], q.shape[-1]
+    if kv is None:
+        kv = torch.arange(H) // (H // K.shape[0])
+    Kh, Vh = K[kv], V[kv]
+    s = (q @ Kh.transpose(1, 2)) / math.sqrt(hd)
+    p = torch.softmax(s.masked_fill(~mask[None], float("-inf")), -1).nan_to_num(0.0)
+    return (p @ Vh).permute(1, 0, 2), (p @ Vh.abs()).permute(1, 0, 2), p
+
+
+def _emulate(q, K, V, mask, dtype=torch.float32, rescale=True, p_bf16=False):
+    """The kernels' order in `dtype`: 64-key chunks, per-chunk max / sum / P.V, then the combine with
+    the chunk weights exp(m_c - m) (rescale=False: the combine without them, a mutation).  p_bf16: P
+    rounded to bf16 and summed rounded, as k_attn_extend_part does.  -> [S, H, hd]."""
+    H, S, hd = q.shape
+    R, N = H // K.shape[0], K.shape[1]
+    nch = (N + 63) // 64
+    padk = lambda t: torch.nn.functional.pad(t.to(dtype), (0, 0, 0, nch * 64 - N)).repeat_interleave(R, 0).view(H, nch, 64, hd)
+    Kh, Vh = padk(K), padk(V)
+    mk = torch.nn.functional.pad(mask, (0, nch * 64 - N)).view(S, nch, 64)[None]
+    s = torch.einsum("hsd,hckd->hsck", q.to(dtype), Kh) * torch.tensor(1.0 / math.sqrt(hd), dtype=dtype)
+    s = s.masked_fill(~mk, float("-inf"))
+    m = s.amax(-1)
+    p = torch.where(mk, torch.exp(s - m[..., None]), torch.zeros((), dtype=dtype))
+    if p_bf16:
+        p = p.to(BF).to(dtype)
+    l = p.sum(-1)
+    acc = torch.einsum("hsck,hckd->hscd", p, Vh)
+    live = m > float("-inf")
+    w = torch.where(live, torch.exp(m - m.amax(-1, keepdim=True)), torch.zeros((), dtype=dtype)) if rescale else live.to(dtype)
+    o = (w[..., None] * acc).sum(2) / (w * l).sum(2)[..., None]
+    return o.permute(1, 0, 2)
+
+
+def _reference(Q):
+    """fp64 reference of a question: (o, P|V|) [S, H, hd] and the probe's weight [S, H]."""
+    o, pabs, p = _attend(Q.q, Q.K, Q.V, _causal(Q))
+    w = p[:, :, Q.probe].t() if Q.probe is not None else None
+    return o, pabs, w
+
+
+def _dec_excess(got, ref, pabs):
+    """(|err| - 2^-8 |ref|) / P|V|, the quantity the decode bound keeps below C_DEC (NaN -> inf)."""
+    x = ((got.double() - ref).abs() - 2.0 ** -8 * ref.abs()) / pabs
+    return float(x.nan_to_num(float("inf")).max())
+
+
+def _ext_ok(got, ref, pabs, rms):
+    err = (got.double() - ref).abs()
+    return bool((err <= 2e-2 * rms + 2e-2 * ref.abs() + 2.0 ** -8 * pabs).all())
+
+
+def _note(kernel, x):
+    WORST[kernel] = max(WORST.get(kernel, float("-inf")), x)
+
+
+# --------------------------------------------------------------------------- decode cases ----
+
+SHAPES = [(64, 14, 2), (128, 28, 4)]
+LENGTHS = (1, 2, 63, 64, 65, 128, 129, 256)   # smax = 256: n = 256 is the last slot
+# (hd, H, HKV, smax, n, hdp); the hdp = hd + 8 case carries poison in the padding columns
+DECODE_CASES = [(hd, H, HKV, 256, n, hd) for hd, H, HKV in SHAPES for n in LENGTHS]
+DECODE_CASES += [(hd, H, HKV, 1600, 1537, hd) for hd, H, HKV in SHAPES]   # the workload's own length
+DECODE_CASES += [(64, 2, 1, 32768, 32768, 64)]   # nch = 512 = MAX_CH: second pass of the combine loops, last slot
+DECODE_CASES += [(64, 14, 2, 256, 129, 72)]
+# decode_batch: the same runs, the main lengths as the rows of one call with per-row cur
+BATCH_CASES = [(hd, H, HKV, 256, LENGTHS, hd) for hd, H, HKV in SHAPES]
+BATCH_CASES += [(hd, H, HKV, 1600, (1537,), hd) for hd, H, HKV in SHAPES]
+BATCH_CASES += [(64, 2, 1, 32768, (32768,), 64), (64, 14, 2, 256, (129, 64, 2), 72)]
+
+
+def _case_id(c):
+    hd, H, HKV, smax, n, hdp = c
+    ns = f"n{n}" if isinstance(n, int) else n if isinstance(n, str) else "rows" + "_".join(str(x) for x in n)
+    return f"hd{hd}-H{H}-kv{HKV}-smax{smax}-{ns}" + (f"-hdp{hdp}" if hdp != hd else "")
+
+
+def _probes(n):
+    return sorted({p for p in (0, 63, 64, n - 2, n - 1) if 0 <= p < n})
+
+
+@functools.lru_cache(maxsize=None)
+def _decode_runs(hd, H, HKV, n):
+    """One run per probe position of a decode case: (question, fp64 reference, P|V|)."""
+    runs = []
+    for p in _probes(n):
+        Q = _question(hd, H, HKV, n - 1, 1, p)
+        ref, pabs, w = _reference(Q)
+        if n > 1:   # both the probe and the rest matter
+            assert 0.25 <= float(w.min()) and float(w.max()) <= 0.75, (hd, H, HKV, n, p, float(w.min()), float(w.max()))
+        else:
+            assert float(w.min()) == 1.0
+        runs.append((Q, ref[0], pabs[0]))
+    return runs
+
+
+@functools.lru_cache(maxsize=None)
+def _range_run(hd, H, HKV, n, kind):
+    Q = _question(hd, H, HKV, n - 1, 1, None, kind)
+    ref, pabs, _ = _reference(Q)
+    return Q, ref[0], pabs[0]
+
+
+def _decode_mutations(Q):
+    """Wrong results a decode attention kernel can produce, as fp64 mutations of the reference."""
+    n, p, R = Q.N, Q.probe, Q.H // Q.HKV
+    mask = torch.ones(1, n, dtype=torch.bool)
+    pv = torch.full_like(Q.V[:, :1], POISON_V)
+    K2, V2 = Q.K.clone(), Q.V.clone()
+    K2[:, p], V2[:, p] = 0, 0
+    yield "probe key and value zeroed", _attend(Q.q, K2, V2, mask)[0][0]
+    m2 = mask.clone()
+    m2[:, p // 64 * 64:p // 64 * 64 + 64] = False
+    yield "the probe's chunk dropped", _attend(Q.q, Q.K, Q.V, m2)[0][0]
+    yield "position n attended", _attend(Q.q, torch.cat([Q.K, Q.pk[:, None]], 1), torch.cat([Q.V, pv], 1),
+                                          torch.ones(1, n + 1, dtype=torch.bool))[0][0]
+    K2, V2 = Q.K.clone(), Q.V.clone()
+    K2[:, n - 1], V2[:, n - 1] = Q.pk, POISON_V
+    yield "n - 1 taken from the stale cache", _attend(Q.q, K2, V2, mask)[0][0]
+    if n > 64:
+        yield "chunks combined without the max rescale", _emulate(Q.q, Q.K, Q.V, mask, F64, rescale=False)[0]
+    if Q.HKV > 1:
+        kv = torch.arange(Q.H) // R
+        kv[-1] = 0
+        yield "the last query head reading kv head 0", _attend(Q.q, Q.K, Q.V, mask, kv)[0][0]
+
+
+# --------------------------------------------------------------------------- extend cases ----
+
+EXT_KINDS = ("p0", "base-1", "base", "last")   # one probe position per run, for every question of the call
+EXT_SHAPES = [(64, 14, 2, 64), (128, 28, 4, 128), (64, 14, 2, 72)]   # hd, H, HKV, hdp
+
+
+def _ext_probe(kind, base, S):
+    return {"p0": 0, "base-1": base - 1, "base": base, "last": base + S - 1}[kind]
+
+
+@functools.lru_cache(maxsize=None)
+def _extend_run(hd, H, HKV, kind):
+    """The QUESTIONS of one call with the probe at `kind`: questions, references, rms of the call's reference."""
+    Qs, refs = [], []
+    for base, S in QUESTIONS:
+        Q = _question(hd, H, HKV, base, S, _ext_probe(kind, base, S))
+        ref, pabs, w = _reference(Q)
+        sees = (Q.probe <= Q.base + torch.arange(S))[:, None].expand(S, H)
+        assert bool(sees.any())
+        # the last row always sees the probe; rows that do give it about half, rows that do not give it nothing
+        assert 0.25 <= float(w[sees].min()) and float(w[sees].max()) <= 0.75, (kind, base, S, float(w[sees].min()), float(w[sees].max()))
+        assert not bool(w[~sees].any())
+        Qs.append(Q)
+        refs.append((ref, pabs))
+    rms = float(torch.cat([r for r, _ in refs]).pow(2).mean().sqrt())
+    return Qs, refs, rms
+
+
+def _extend_mutations(Q):
+    base, S, N = Q.base, Q.S, Q.N
+    mask = _causal(Q)
+    m2 = mask.clone()
+    m2[:, Q.probe] = False
+    yield "the probe dropped", _attend(Q.q, Q.K, Q.V, m2)[0]
+    if S > 1:
+        m2 = mask.clone()
+        for j in range(S - 1):
+            m2[j, base + j + 1] = True
+        yield "a suffix row seeing the next suffix key", _attend(Q.q, Q.K, Q.V, m2)[0]
+    K2, V2 = Q.K.clone(), Q.V.clone()
+    K2[:, base], V2[:, base] = Q.pk, POISON_V
+    yield "position base read from the cache", _attend(Q.q, K2, V2, mask)[0]
+
+
+# ------------------------------------------------------------------------------------ CPU ----
+
+@pytest.mark.parametrize("case", DECODE_CASES + [(hd, H, HKV, SMAX, "extend", hdp) for hd, H, HKV, hdp in EXT_SHAPES[:2]],
+                         ids=_case_id)
+def test_probe_poison_bounds_reject_mutations(case):
+    """The test of the tests.  Decode cases: (a) the bf16-rounded fp32 chunked emulation passes the
+    bound in every probe run, (b) every mutation -- probe key and value zeroed; the probe's chunk
+    dropped; position n attended (poison); n - 1 taken from the stale cache (poison); chunks combined
+    without the max rescale (n > 64); the last query head reading kv head 0 (HKV > 1) -- fails it
+    in at least one probe run.  The sink and all-scores-below--150 inputs of the score-range tests:
+    (a) only.  Extend (the QUESTIONS call, its own bound), per question: (a) with P rounded to
+    bf16, (b) the probe dropped; a suffix row seeing the next suffix key (S > 1); position base
+    read from the cache."""
+    hd, H, HKV, smax, n, hdp = case
+    if n == "extend":
+        rejected = {}
+        for kind in EXT_KINDS:
+            Qs, refs, rms = _extend_run(hd, H, HKV, kind)
+            for b, (Q, (ref, pabs)) in enumerate(zip(Qs, refs)):
+                emu = _emulate(Q.q, Q.K, Q.V, _causal(Q), p_bf16=True).to(BF)
+                assert _ext_ok(emu, ref, pabs, rms), (kind, b)
+                for name, mut in _extend_mutations(Q):
+                    rejected[(b, name)] = rejected.get((b, name), False) or not _ext_ok(mut, ref, pabs, rms)
+        assert len(rejected) == sum(3 if S > 1 else 2 for _, S in QUESTIONS)
+        assert all(rejected.values()), [k for k, v in rejected.items() if not v]
+        return
+    rejected = {}
+    for Q, ref, pabs in _decode_runs(hd, H, HKV, n):
+        emu = _emulate(Q.q, Q.K, Q.V, torch.ones(1, n, dtype=torch.bool))[0].to(BF)
+        x = _dec_excess(emu, ref, pabs)
+        assert x <= C_DEC, (Q.probe, x)
+        for name, mut in _decode_mutations(Q):
+            rejected[name] = rejected.get(name, False) or _dec_excess(mut, ref, pabs) > C_DEC
+    assert len(rejected) == 4 + (n > 64) + (HKV > 1)
+    assert all(rejected.values()), [k for k, v in rejected.items() if not v]
+    if (smax, n, hdp) == (256, 256, hd):   # the score-range inputs ride on one case per shape
+        for kind in ("sink", "low"):
+            for nn in RANGE_N:
+                Q, ref, pabs = _range_run(hd, H, HKV, nn, kind)
+                emu = _emulate(Q.q, Q.K, Q.V, torch.ones(1, nn, dtype=torch.bool))[0].to(BF)
+                assert _dec_excess(emu, ref, pabs) <= C_DEC, (kind, nn)
+                if kind == "sink":
+                    assert torch.equal(emu.double(), ref.to(BF).double())
+                    assert torch.equal(ref.to(BF), Q.V[:, 0].repeat_interleave(H // HKV, 0))
+
+
+# --------------------------------------------------------------------- GPU: decode, batch ----
+
+def _pad(t, hdp):
+    """[..., hd] bf16 -> [..., hdp] with poison in the padding columns"""
+    hd = t.shape[-1]
+    if hdp == hd:
+        return t.contiguous()
+    out = torch.full((*t.shape[:-1], hdp), POISON_V, dtype=BF)
+    out[..., :hd] = t
+    return out
+
+
+def _caches(Q, smax, hdp):
+    """Caches [HKV, smax, hdp] as the call finds them: the true rows below base, poison from base on
+    (the rows the call stores to, stale, and everything past the end) and in the padding columns."""
+    kc = torch.full((Q.HKV, smax, hdp), POISON_V, dtype=BF)
+    vc = torch.full((Q.HKV, smax, hdp), POISON_V, dtype=BF)
+    kc[:, :, :Q.hd] = Q.pk[:, None, :]
+    kc[:, :Q.base, :Q.hd] = Q.K[:, :Q.base]
+    vc[:, :Q.base, :Q.hd] = Q.V[:, :Q.base]
+    return kc, vc
+
+
+def _run_decode(ops, dev, Q, smax, hdp):
+    """kd_attn_decode on a question with host n and with the device counter: the same bits, the own
+    row (all hdp columns) stored at n - 1 and no other cache element changed.  -> o [H, hd] on the CPU"""
+    n = Q.N
+    kc, vc = _caches(Q, smax, hdp)
+    q, kn, vn = _pad(Q.q[:, 0], hdp).to(dev), _pad(Q.K[:, n - 1], hdp).to(dev), _pad(Q.V[:, n - 1], hdp).to(dev)
+    want_k, want_v = kc.to(dev), vc.to(dev)
+    want_k[:, n - 1], want_v[:, n - 1] = kn, vn
+    outs = []
+    for cur in (None, torch.tensor([n], dtype=torch.int32, device=dev)):
+        kcd, vcd = kc.to(dev), vc.to(dev)
+        o = ops.attn_decode(q, kn, vn, kcd, vcd, n if cur is None else 0, Q.hd, cur=cur)
+        assert torch.equal(kcd, want_k) and torch.equal(vcd, want_v), (n, Q.probe, cur is None)
+        assert cur is None or int(cur) == n
+        outs.append(o.view(Q.H, Q.hd).cpu())
+    assert torch.equal(outs[0], outs[1])
+    return outs[0]
+
+
+def _run_decode_batch(ops, dev, Qs, smax, hdp):
+    """kd_attn_decode_batch with row b = question Qs[b], per-row cur.  -> o [nb, H, hd] on the CPU"""
+    nb, Q0 = len(Qs), Qs[0]
+    cs = [_caches(Q, smax, hdp) for Q in Qs]
+    kc, vc = torch.stack([c[0] for c in cs]).to(dev), torch.stack([c[1] for c in cs]).to(dev)
+    q = _pad(torch.stack([Q.q[:, 0] for Q in Qs], 1), hdp).to(dev)
+    kn = _pad(torch.stack([Q.K[:, Q.N - 1] for Q in Qs], 1), hdp).to(dev)
+    vn = _pad(torch.stack([Q.V[:, Q.N - 1] for Q in Qs], 1), hdp).to(dev)
+    want_k, want_v = kc.clone(), vc.clone()
+    for b, Q in enumerate(Qs):
+        want_k[b, :, Q.N - 1], want_v[b, :, Q.N - 1] = kn[:, b], vn[:, b]
+    cur = torch.tensor([Q.N for Q in Qs], dtype=torch.int32, device=dev)
+    o = ops.attn_decode_batch(q, kn, vn, kc, vc, cur, Q0.hd)
+    assert torch.equal(kc, want_k) and torch.equal(vc, want_v)
+    assert cur.cpu().tolist() == [Q.N for Q in Qs]
+    return o.view(nb, Q0.H, Q0.hd).cpu()
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("case", DECODE_CASES, ids=_case_id)
+def test_gpu_attn_decode_probe_poison(case, dev):
+    """kd_attn_decode, one launch pair (host n / device counter) per probe position in
+    {0, 63, 64, n - 2, n - 1} (at n - 1 the probe lives in k_new / v_new only), poison in every
+    cache row >= n - 1 and, for hdp = hd + 8, in the padding columns."""
+    hd, H, HKV, smax, n, hdp = case
+    ops = _ops()
+    for Q, ref, pabs in _decode_runs(hd, H, HKV, n):
+        x = _dec_excess(_run_decode(ops, dev, Q, smax, hdp), ref, pabs)
+        print(f"kd_attn_decode {_case_id(case)} probe {Q.probe}: (|err| - 2^-8|ref|) / P|V| = {x:.3e} (bound {C_DEC:g})")
+        _note("kd_attn_decode", x)
+        assert x <= C_DEC, (Q.probe, x)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("case", BATCH_CASES, ids=_case_id)
+def test_gpu_attn_decode_batch_probe_poison(case, dev):
+    """kd_attn_decode_batch: the rows of one call are the case's lengths (per-row cur); launch k
+    puts row b's probe at the k-th of its positions {0, 63, 64, n - 2, n - 1}."""
+    hd, H, HKV, smax, ns, hdp = case
+    ops = _ops()
+    runs = [_decode_runs(hd, H, HKV, n) for n in ns]
+    for k in range(max(len(r) for r in runs)):
+        pick = [r[k % len(r)] for r in runs]
+        o = _run_decode_batch(ops, dev, [Q for Q, _, _ in pick], smax, hdp)
+        for b, (Q, ref, pabs) in enumerate(pick):
+            x = _dec_excess(o[b], ref, pabs)
+            print(f"kd_attn_decode_batch {_case_id(case)} row n={Q.N} probe {Q.probe}: "
+                  f"(|err| - 2^-8|ref|) / P|V| = {x:.3e} (bound {C_DEC:g})")
+            _note("kd_attn_decode_batch", x)
+            assert x <= C_DEC, (Q.N, Q.probe, x)
+
+
+RANGE_N = (200, 130)   # four chunks with a partial last one; three chunks
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("kind", ["sink", "low"])
+@pytest.mark.parametrize("hd,H,HKV", SHAPES)
+def test_gpu_attn_decode_score_range(hd, H, HKV, kind, dev):
+    """sink: position 0 scores about +60 and every other key about -40, so every chunk weight but
+    the first underflows to exactly 0 in the combine: the result is v[0], no NaN.  low: every score
+    about -200 (k = -gamma' u): a proper softmax, no 0/0.  kd_attn_decode at n = 200 and
+    kd_attn_decode_batch on rows n = 200 and n = 130."""
+    ops = _ops()
+    runs = [_range_run(hd, H, HKV, n, kind) for n in RANGE_N]
+    single = _run_decode(ops, dev, runs[0][0], 256, hd)
+    batch = _run_decode_batch(ops, dev, [r[0] for r in runs], 256, hd)
+    for name, got, (Q, ref, pabs) in (("kd_attn_decode", single, runs[0]), ("kd_attn_decode_batch", batch[0], runs[0]),
+                                      ("kd_attn_decode_batch", batch[1], runs[1])):
+        assert bool(torch.isfinite(got.float()).all())
+        x = _dec_excess(got, ref, pabs)
+        print(f"{name} {kind} hd{hd} n={Q.N}: (|err| - 2^-8|ref|) / P|V| = {x:.3e} (bound {C_DEC:g})")
+        _note(name, x)
+        assert x <= C_DEC, (name, Q.N, x)
+        if kind == "sink":
+            assert torch.equal(got, Q.V[:, 0].repeat_interleave(H // HKV, 0))
+
+
+# --------------------------------------------------------------------------- GPU: extend ----
+
+def _run_extend(ops, dev, Qs, smax, hdp):
+    """kd_attn_extend over the questions in one call; afterwards cache positions [base, base + S)
+    hold the suffix rows (all hdp columns), every other element, poison included, is bit-identical
+    to before.  -> o [rows, H, hd] on the CPU"""
+    Q0 = Qs[0]
+    starts = [0]
+    for Q in Qs:
+        starts.append(starts[-1] + Q.S)
+    cs = [_caches(Q, smax, hdp) for Q in Qs]
+    kc, vc = torch.stack([c[0] for c in cs]).to(dev), torch.stack([c[1] for c in cs]).to(dev)
+    q = _pad(torch.cat([Q.q for Q in Qs], 1), hdp).to(dev)
+    kn = _pad(torch.cat([Q.K[:, Q.base:] for Q in Qs], 1), hdp).to(dev)
+    vn = _pad(torch.cat([Q.V[:, Q.base:] for Q in Qs], 1), hdp).to(dev)
+    want_k, want_v = kc.clone(), vc.clone()
+    for b, Q in enumerate(Qs):
+        want_k[b, :, Q.base:Q.N] = kn[:, starts[b]:starts[b + 1]]
+        want_v[b, :, Q.base:Q.N] = vn[:, starts[b]:starts[b + 1]]
+    row_start = torch.tensor(starts, dtype=torch.int32, device=dev)
+    base = torch.tensor([Q.base for Q in Qs], dtype=torch.int32, device=dev)
+    o = ops.attn_extend(q, kn, vn, kc, vc, row_start, base, Q0.hd)
+    assert torch.equal(kc, want_k) and torch.equal(vc, want_v)
+    return o.view(starts[-1], Q0.H, Q0.hd).cpu()
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("hd,H,HKV,hdp", EXT_SHAPES, ids=lambda v: str(v))
+def test_gpu_attn_extend_probe_poison(hd, H, HKV, hdp, dev):
+    """kd_attn_extend on the QUESTIONS (base, S) pairs in one call, one launch per probe position:
+    prefix position 0; base - 1; base (the first suffix row, from k_new); the last suffix key
+    base + S - 1, to which every earlier suffix row must give weight 0 (the causal-leak detector)
+    and the last row about half.  Poison in every cache row >= base and, for hdp = hd + 8 (which
+    the launcher accepts), in the padding columns."""
+    ops = _ops()
+    for kind in EXT_KINDS:
+        Qs, refs, rms = _extend_run(hd, H, HKV, kind)
+        o = _run_extend(ops, dev, Qs, SMAX, hdp)
+        ref, pabs = torch.cat([r for r, _ in refs]), torch.cat([p for _, p in refs])
+        x = _dec_excess(o, ref, pabs)
+        print(f"kd_attn_extend hd{hd} hdp{hdp} probe at {kind}: (|err| - 2^-8|ref|) / P|V| = {x:.3e} "
+              f"(bound: 2e-2 rms + 2e-2 |ref| + 2^-8 P|V|)")
+        _note("kd_attn_extend", x)
+        assert _ext_ok(o, ref, pabs, rms), (kind, x)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("hd,H,HKV", SHAPES)
+def test_gpu_attn_extend_score_range(hd, H, HKV, dev):
+    """One call, two questions: (base 200, S 3) with the sink at prefix position 0 (+60 against
+    -40: every row is v[0], no NaN) and (base 70, S 5) with every score about -200."""
+    ops = _ops()
+    Qs = [_question(hd, H, HKV, 200, 3, None, "sink"), _question(hd, H, HKV, 70, 5, None, "low")]
+    refs = [_reference(Q)[:2] for Q in Qs]
+    o = _run_extend(ops, dev, Qs, SMAX, hd)
+    assert bool(torch.isfinite(o.float()).all())
+    assert torch.equal(o[:3], Qs[0].V[:, 0].repeat_interleave(H // HKV, 0)[None].expand(3, H, hd))
+    ref, pabs = torch.cat([r for r, _ in refs]), torch.cat([p for _, p in refs])
+    assert _ext_ok(o, ref, pabs, float(ref.pow(2).mean().sqrt()))
+
+
+# ---------------------------------------------------------------------- GPU: token choice ----
+
+def _select_single(ops, dev, lg, seq, penalty, ngram, form, off=0):
+    """kd_gen_select on bf16 scores lg [V] placed `off` elements past a 16-byte boundary, with the
+    host length ("len") or the device counter ("cur"); == the oracle, seq untouched below len."""
+    V, seq = lg.numel(), [int(t) for t in seq]
+    buf = torch.zeros(V + 8, dtype=BF, device=dev)
+    view = buf[off:off + V]
+    view.copy_(lg)
+    assert view.data_ptr() % 16 == 2 * off
+    s = torch.tensor(seq + [-1], dtype=torch.int64, device=dev)
+    out = torch.full((1,), -1, dtype=torch.int64, device=dev)
+    if form == "cur":
+        cur = torch.tensor([len(seq)], dtype=torch.int32, device=dev)
+        ops.gen_select(view[None], s, 0, penalty, ngram, out=out, cur=cur)
+        assert int(cur) == len(seq) + 1
+    else:
+        ops.gen_select(view[None], s, len(seq), penalty, ngram, out=out)
+    want = G.select(lg.float().numpy(), seq, penalty, ngram)
+    s = s.cpu().tolist()
+    assert s[:-1] == seq
+    assert int(out) == want == s[-1], (V, off, form, int(out), want)
+    return want
+
+
+def _select_batch(ops, dev, rows, smax, penalty, ngram, pad=0):
+    """kd_gen_select_batch on rows [(lg [V], seq)] with logits rows V + pad apart: every out[b] == the
+    oracle, seq untouched except seq[b, len] (nothing at all when len == smax), cur incremented."""
+    nb, V = len(rows), rows[0][0].numel()
+    buf = torch.zeros(nb, V + pad, dtype=BF, device=dev)
+    logits = buf[:, :V]
+    seq = torch.full((nb, smax), -1, dtype=torch.int64)
+    for b, (lg, sq) in enumerate(rows):
+        logits[b].copy_(lg)
+        seq[b, :len(sq)] = torch.tensor([int(t) for t in sq], dtype=torch.int64)
+    seq_d = seq.to(dev)
+    lens = [len(sq) for _, sq in rows]
+    want = [G.select(lg.float().numpy(), [int(t) for t in sq], penalty, ngram) for lg, sq in rows]
+    for b in range(nb):   # what the call must leave behind
+        if lens[b] < smax:
+            seq[b, lens[b]] = want[b]
+    cur = torch.tensor(lens, dtype=torch.int32, device=dev)
+    out = torch.full((nb,), -1, dtype=torch.int64, device=dev)
+    ops.gen_select_batch(logits, seq_d, cur, penalty, ngram, out=out)
+    assert out.cpu().tolist() == want, (out.cpu().tolist(), want)
+    assert torch.equal(seq_d.cpu(), seq)
+    assert cur.cpu().tolist() == [n + 1 for n in lens]
+    return want
+
+
+def _scores(V, seed, scale=3.0):
+    g = np.random.default_rng(seed)
+    return torch.from_numpy((g.standard_normal(V) * scale).astype(np.float32)).to(BF)
+
+
+VS = (1, 7, 8, 9, 15, 17, 8197, 151936)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("off", [0, 1, 4], ids=["aligned", "plus2bytes", "plus8bytes"])
+@pytest.mark.parametrize("V", VS)
+def test_gpu_gen_select_tails_and_alignment(V, off, dev):
+    """The scalar tails (V & 15 of the flag clear, V & 7 of the argmax) and the unaligned fallback
+    (logits 2 and 8 bytes past a 16-byte boundary: v8 = 0), both forms of the kernel; the winner is
+    planted in the tail (V - 1), in the middle and at index 0, seen ids are spread over [0, V)."""
+    ops = _ops()
+    g = np.random.default_rng(V + off)
+    for k, win in enumerate((V - 1, V // 2, 0)):
+        lg = _scores(V, 10 * V + k)
+        lg[win] = 20.0
+        seq = list(g.integers(0, V, 40)) + [V - 1] * (k == 1)   # k == 1: the tail id is seen (and banned after itself)
+        want = _select_single(ops, dev, lg, seq, 1.2, 2, "cur" if (k + off) % 2 else "len", off)
+        if win not in seq:
+            assert want == win
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("ldl_pad", [0, 1, 4], ids=["ldl=V", "ldl=V+1", "ldl=V+4"])
+def test_gpu_gen_select_batch_row_strides(ldl_pad, dev):
+    """V = 8197, nb = 3: rows 1 and 2 of the logits start 10 / 12 / 2 bytes past a 16-byte boundary
+    and the flag rows b * V are odd, so the vector body and the 16-byte flag clear are both off for
+    them; row b's winner is planted in the tail, in the body, at index 0."""
+    ops = _ops()
+    V, g, rows = 8197, np.random.default_rng(ldl_pad), []
+    for b, win in enumerate((V - 1, 4099, 0)):
+        lg = _scores(V, 77 + b)
+        lg[win] = 20.0
+        rows.append((lg, list(g.integers(0, V - 1, 30 + b)) + [1, 2][:b]))
+    want = _select_batch(ops, dev, rows, 64, 1.2, 2, ldl_pad)
+    assert want == [V - 1, 4099, 0]
+    for lg, sq in rows:   # and every row == kd_gen_select on it alone
+        _select_single(ops, dev, lg, sq, 1.2, 2, "len")
+
+
+TIE_SETS = ([21, 4099, 8191, 8196], [4099, 8191, 8196], [8191, 8196], [8196], [5, 8196])
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("off", [0, 1], ids=["vector", "scalar"])
+def test_gpu_gen_select_planted_ties(off, dev):
+    """V = 8197, the same maximum at several indices; the lowest must win wherever it sits: 21 (lane
+    2 of wave 0 in the vector body), 4099 (wave 8), 8191 (the body's last element, wave 15, against
+    the scalar tail's 8196, which thread 4 of wave 0 holds), 8196 alone, 5 (lane 0) against the tail;
+    then two ties inside one thread's own strided trips at V = 151936.  Single kernel (both forms)
+    and all sets as the rows of one batched call (ldl = V and V + 1)."""
+    ops = _ops()
+    V, rows = 8197, []
+    for k, idx in enumerate(TIE_SETS):
+        lg = _scores(V, 500 + k)
+        lg[idx] = 17.0
+        rows.append((lg, [3, 9]))
+        assert _select_single(ops, dev, lg, [3, 9], 1.2, 2, "cur" if k % 2 else "len", off) == min(idx)
+    assert _select_batch(ops, dev, rows, 8, 1.2, 2, off) == [min(i) for i in TIE_SETS]
+    V = 151936
+    for idx in ([16 + 8192, 16 + 3 * 8192], [1029, 1029 + 1024 * 5, V - 1]):
+        lg = _scores(V, idx[0])
+        lg[idx] = 40.0
+        assert _select_single(ops, dev, lg, [3, 9], 1.2, 2, "len", off) == min(idx)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("V", [8197, 151936])
+def test_gpu_gen_select_processor_made_ties(V, dev):
+    """Ties that only exist after the processors ran (penalty 1.5, IEEE division and multiplication):
+    a seen 12.0 -> 8.0 against unseen 8.0 below it, above it, on both sides; a seen -4.0 -> -6.0
+    against unseen -6.0; a banned token that would have won."""
+    ops = _ops()
+    base = (-10 - _scores(V, 1).float().abs()).to(BF)
+    lo, seen, hi = 100, V // 2, V - 3
+
+    def run(vals, seq, ngram=0):
+        lg = base.clone()
+        for i, v in vals.items():
+            lg[i] = v
+        got = {_select_single(ops, dev, lg, seq, 1.5, ngram, form) for form in ("len", "cur")}
+        got.add(_select_batch(ops, dev, [(lg, seq), (base, [0])], 16, 1.5, ngram, 1)[0])
+        assert len(got) == 1
+        return got.pop()
+
+    assert run({lo: 8.0, seen: 12.0, hi: 8.0}, [seen, 1]) == lo
+    assert run({seen: 12.0, hi: 8.0}, [seen, 1]) == seen
+    assert run({lo: 8.0, seen: 12.0}, [seen, 1]) == lo
+    assert run({seen: 12.0, hi: 7.96875}, [seen, 1]) == seen
+    assert run({lo: -6.0, seen: -4.0, hi: -6.0}, [seen, 1]) == lo
+    assert run({seen: -4.0, hi: -6.0}, [seen, 1]) == seen
+    assert run({seen: -4.0, hi: -5.96875}, [seen, 1]) == hi
+    # bigram (7, seen) occurred and the sequence ends on 7: seen is banned, the runner-up wins
+    assert run({seen: 30.0, hi: 8.0}, [7, seen, 2, 7], ngram=2) == hi
+    assert run({seen: 30.0, hi: 8.0}, [7, seen, 2, 5], ngram=2) == seen
+
+
+@pytest.mark.gpu
+def test_gpu_gen_select_every_score_minus_inf(dev):
+    """All logits -inf; the only finite token banned by the n-gram rule; V = 1 with a ban: each
+    returns 0, as argmax does.  Single kernel (both forms, both alignments) and batched."""
+    ops = _ops()
+    ninf = float("-inf")
+    cases = []
+    for V in (8197, 17):
+        cases.append((torch.full((V,), ninf, dtype=BF), [4, 5, 4]))
+        lg = torch.full((V,), ninf, dtype=BF)
+        lg[11] = 2.0
+        cases.append((lg, [4, 11, 6, 4]))   # after (4, 11) and a last token 4, 11 is banned
+    cases.append((torch.tensor([1.5], dtype=BF), [0, 0, 0]))
+    for lg, seq in cases:
+        for form, off in (("len", 0), ("cur", 1)):
+            assert _select_single(ops, dev, lg, seq, 1.2, 2, form, off) == 0
+        assert _select_batch(ops, dev, [(lg, seq), (lg, seq[:-1])], 8, 1.2, 2, 1)[0] == 0
+    lg = torch.full((8197,), ninf, dtype=BF)
+    lg[11] = 2.0
+    assert _select_single(ops, dev, lg, [4, 11, 6, 5], 1.2, 2, "len") == 11   # not banned: the finite one
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("ngram", [1, 2, 3, 4])
+def test_gpu_gen_select_len_around_ngram(ngram, dev):
+    """len in {1, ngram - 2, ngram - 1, ngram, ngram + 1} (positive ones) of a repeated id whose score
+    would win: the ban starts exactly at len == ngram (ngram = 1: at once, every seen id)."""
+    ops = _ops()
+    V = 8197
+    lg = _scores(V, ngram)
+    lg[7], lg[4100] = 30.0, 20.0
+    for n in sorted({x for x in (1, ngram - 2, ngram - 1, ngram, ngram + 1) if x > 0}):
+        for form in ("len", "cur"):
+            got = _select_single(ops, dev, lg, [7] * n, 1.2, ngram, form)
+            assert got == (4100 if n >= ngram else 7), (ngram, n, got)
+        rows = [(lg, [7] * n), (lg, [7] * (n + 1)), (lg, [7, 8] * 2)]
+        _select_batch(ops, dev, rows, 8, 1.2, ngram, 1)
+
+
+def _long_seq(n, V, seed):
+    """n distinct ids out of [100, V - 100): nothing repeats, no n-gram matches"""
+    return list(np.random.default_rng(seed).permutation(np.arange(100, V - 100))[:n])
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("ngram", [2, 3])
+def test_gpu_gen_select_len_2500(ngram, dev):
+    """The second and third trips of the 1024-thread loops over the sequence (a real prompt is 1500
+    to 3000 ids).  Distinct ids but for: (a) the only matching prefix at i = 1500; (b) the only
+    matching prefix at the last valid i = len - ngram; (c) the would-be winner seen only at index
+    2100 (penalised below the runner-up)."""
+    ops = _ops()
+    V, n = 8197, 2500
+    lg = _scores(V, 9 + ngram)
+    top, second = 50, 8150
+    lg[top], lg[second] = 30.0, 29.0
+    # (a) seq[1500 : 1500 + ngram - 1] == the last ngram - 1 ids, followed by `top`
+    a = _long_seq(n, V, 1)
+    a[1500 + ngram - 1] = top
+    a[n - ngram + 1:] = a[1500:1500 + ngram - 1]
+    # (b) the match starts at i = n - ngram: seq[i : i + ngram - 1] == seq[i + 1 : n], so all of the last ngram ids are equal
+    b = _long_seq(n, V, 2)
+    b[n - ngram:] = [top] * ngram
+    # (c) seen at 2100 only: 30 / 1.2 = 25 < 29
+    c = _long_seq(n, V, 3)
+    c[2100] = top
+    for seq, penalty in ((a, 1.0), (b, 1.0), (c, 1.2)):
+        for form in ("len", "cur"):
+            assert _select_single(ops, dev, lg, seq, penalty, ngram, form) == second
+    d = _long_seq(n, V, 4)   # nothing seen, nothing banned: the winner stays
+    assert _select_single(ops, dev, lg, d, 1.2, ngram, "len") == top
+    assert _select_batch(ops, dev, [(lg, a), (lg, b), (lg, d)], n + 1, 1.0, ngram, 4) == [second, second, top]
+    assert _select_batch(ops, dev, [(lg, c), (lg, d)], n + 1, 1.2, ngram, 0) == [second, top]
+
+
+@pytest.mark.gpu
+def test_gpu_gen_select_batch_ragged_rows_do_not_leak(dev):
+    """One call with lens {1, 3, 1030, 2500} (V = 8197, ldl = V + 1): every row equals kd_gen_select on
+    that row alone and the oracle; the id row b sees and bans (its bigram (x, id) with a last token
+    x; row 0 is too short to ban) is the top logit of row b + 1, so a flag leaking into the next row
+    changes that row's answer; seq is untouched except at seq[b, len], cur is incremented."""
+    ops = _ops()
+    V, lens = 8197, (1, 3, 1030, 2500)
+    tops = [(200 + 1000 * b, 300 + 1000 * b) for b in range(4)]   # (winner, runner-up) of row b
+    rows = []
+    for b, n in enumerate(lens):
+        lg = _scores(V, 40 + b)
+        lg[tops[b][0]], lg[tops[b][1]] = 30.0, 29.0
+        nxt, x = tops[(b + 1) % 4][0], 5000 + b
+        if n == 1:
+            seq = [nxt]
+        elif n == 3:
+            seq = [x, nxt, x]
+        else:   # the bigram sits past index 1024
+            seq = [int(t) for t in _long_seq(n + 20, V, 50 + b)]
+            seq = [t for t in seq if t not in (x, nxt) and all(t not in p for p in tops)][:n - 3]
+            seq = seq[:1026] + [x, nxt] + seq[1026:] + [x]
+            assert len(seq) == n
+        rows.append((lg, seq))
+    want = _select_batch(ops, dev, rows, 2600, 1.2, 2, 1)
+    assert want == [t[0] for t in tops]
+    for (lg, seq), w in zip(rows, want):
+        assert _select_single(ops, dev, lg, seq, 1.2, 2, "cur") == w
+    # the same rows in the other order: what a row gets does not depend on its slot either
+    assert _select_batch(ops, dev, rows[::-1], 2600, 1.2, 2, 1) == want[::-1]
+
+
+@pytest.mark.gpu
+def test_gpu_gen_select_batch_full_row(dev):
+    """A row with cur[b] == smax (include/kdstep.h): out[b] is the oracle's choice over its smax
+    ids, the row -- and the next row's first id behind it -- is unchanged, cur[b] becomes smax + 1."""
+    ops = _ops()
+    V, smax = 8197, 6
+    lg = _scores(V, 3)
+    lg[60], lg[61] = 30.0, 20.0
+    rows = [(lg, [9, 60, 4, 5, 6, 9]), (lg, [1, 2, 3]), (lg, [60] * smax)]
+    assert _select_batch(ops, dev, rows, smax, 1.2, 2, 1) == [61, 60, 61]
+
+
+# ------------------------------------------------------------------------------ GPU: RoPE ----
+
+ROPE_ROWS, ROPE_HH = 50, 288   # hh > 256: the second trip of the copy loop
+
+
+def _rope_tables(dev):
+    g = torch.Generator().manual_seed(5)
+    return torch.randn(ROPE_ROWS, ROPE_HH, generator=g).to(dev), torch.randn(ROPE_ROWS, ROPE_HH, generator=g).to(dev)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("pos", [1, 2, ROPE_ROWS])
+def test_gpu_rope_row_copies_the_table_row(pos, dev):
+    """kd_rope_row: position cur = pos gives exactly table row pos - 1 (cos and sin), and the rows
+    around the one-row destination keep their guard value."""
+    ops = _ops()
+    cos, sin = _rope_tables(dev)
+    cr, sr = torch.full((3, ROPE_HH), -7.0, device=dev), torch.full((3, ROPE_HH), -7.0, device=dev)
+    cur = torch.tensor([pos], dtype=torch.int32, device=dev)
+    ops.rope_row(cos, sin, cur, cr[1], sr[1])
+    assert torch.equal(cr[1], cos[pos - 1]) and torch.equal(sr[1], sin[pos - 1])
+    assert bool((cr[[0, 2]] == -7.0).all()) and bool((sr[[0, 2]] == -7.0).all())
+    assert int(cur) == pos
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("nb", [1, 16, 40])
+def test_gpu_rope_rows_gathers_and_clamps(nb, dev):
+    """kd_rope_rows with mixed positions, among them cur = 0 and cur = table_rows + 3, which clamp to
+    the first and the last table row; nothing is written outside the [nb, hh] destination."""
+    ops = _ops()
+    cos, sin = _rope_tables(dev)
+    pos = [(7 * b + 1) % ROPE_ROWS + 1 for b in range(nb)]
+    checks = [pos]
+    if nb > 1:
+        edge = list(pos)
+        edge[0], edge[1], edge[-1] = 0, ROPE_ROWS + 3, ROPE_ROWS
+        checks.append(edge)
+    else:
+        checks += [[0], [ROPE_ROWS + 3]]
+    for cs in checks:
+        cr, sr = torch.full((nb + 2, ROPE_HH), -7.0, device=dev), torch.full((nb + 2, ROPE_HH), -7.0, device=dev)
+        cur = torch.tensor(cs, dtype=torch.int32, device=dev)
+        ops.rope_rows(cos, sin, cur, cr[1:nb + 1], sr[1:nb + 1])
+        rows = torch.tensor([min(max(c - 1, 0), ROPE_ROWS - 1) for c in cs], device=dev)
+        assert torch.equal(cr[1:nb + 1], cos[rows]) and torch.equal(sr[1:nb + 1], sin[rows])
+        assert bool((cr[[0, nb + 1]] == -7.0).all()) and bool((sr[[0, nb + 1]] == -7.0).all())
+        assert cur.cpu().tolist() == cs
