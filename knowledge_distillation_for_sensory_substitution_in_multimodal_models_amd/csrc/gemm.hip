@@ -219,11 +219,14 @@ inline int pick_gm(int tiles_m, int tiles_n) {
 
 // Block -> tile map: XCD-aware bijective remap (the blocks dispatched to one XCD, b, b+8,
 // ..., get consecutive ids), offset by the launch's first tile, then the grouped order.
-__device__ __forceinline__ void tile_of(int nwg, int tiles_m, int tiles_n, int& tm, int& tn, int tile0 = 0, int gm = 0) {
-    const int b = blockIdx.x;
+__device__ __forceinline__ void tile_of_b(int b, int nwg, int tiles_m, int tiles_n, int& tm, int& tn, int tile0 = 0,
+                                          int gm = 0) {
     const int q8 = nwg / 8, r8 = nwg % 8, x = b % 8;
     const int wg = (x < r8 ? x * (q8 + 1) : r8 * (q8 + 1) + (x - r8) * q8) + b / 8 + tile0;
     tile_grouped(wg, tiles_m, tiles_n, tm, tn, gm);
+}
+__device__ __forceinline__ void tile_of(int nwg, int tiles_m, int tiles_n, int& tm, int& tn, int tile0 = 0, int gm = 0) {
+    tile_of_b(blockIdx.x, nwg, tiles_m, tiles_n, tm, tn, tile0, gm);
 }
 
 template <bool A_MN, bool B_MN>
@@ -1585,6 +1588,31 @@ __global__ void __launch_bounds__(NTH8, 1) k_gemm8(GemmP p_) {
     g8_tile<A_MN, B_MN, EXP>(p, tm, tn, smem);
 }
 
+// A group of 1-4 weight-gradient GEMMs (MN-major x MN-major, fp32 C) as ONE grid of 256 x 256 v8
+// tiles, every member over its whole K: a weight gradient's output is small and its K (the tokens)
+// long, so alone it fills a fraction of the CUs unless K is split -- and a split doubles the
+// CU-time (shorter k-loops under the same fixed tile cost, fp32 partial planes, a reduce launch).
+// Together a layer's weight gradients fill the CUs unsplit.  Workgroups [t0[i], t0[i + 1]) are
+// member i's tiles in that member's own order: the XCD remap runs on the member-local index (the
+// workgroups b, b + 8, ... of one XCD still get consecutive tiles; only which XCD takes which
+// chunk is rotated by t0[i] % 8), with the member's gm / stagger, so every tile runs exactly the
+// g8_tile call of the member's single unsplit k_gemm8<true, true, 0> launch: the same bits.
+constexpr int GROUP_MAX = 4;
+struct GemmGroupP {
+    GemmP p[GROUP_MAX];
+    int t0[GROUP_MAX];   // first workgroup of member i; past the last member: the grid size
+};
+
+__global__ void __launch_bounds__(NTH8, 1) k_gemm8_group(GemmGroupP g) {
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    const int b = blockIdx.x;
+    const int mi = (b >= g.t0[1]) + (b >= g.t0[2]) + (b >= g.t0[3]);
+    const GemmP p = g.p[mi];
+    int tm, tn;
+    tile_of_b(b - g.t0[mi], p.gx, (p.M + 255) / 256, (p.N + 255) / 256, tm, tn, 0, p.gm);
+    g8_tile<true, true, 0>(p, tm, tn, smem);
+}
+
 #ifdef KD_AB_BUILD   // v9: equal speed to v8 on the step's shapes, not in the plan; A/B library only
 #include "gemm_v9.inc"   // tools/ab/gemm_v9.inc: v9 (eight-wave ping-pong)
 #include "gemm_blas.inc"   // tools/ab/gemm_blas.inc: plain GEMMs through hipBLASLt (KD_GEMM_BLAS)
@@ -2596,6 +2624,63 @@ int launch_gemm(const kd_gemm_desc* d, void* stream_) {
     else if (amn && bmn) hipLaunchKernelGGL((k_gemm<true, true>), dim3(tiles), dim3(NTH), smem, st, p);
     else hipLaunchKernelGGL((k_gemm<true, false>), dim3(tiles), dim3(NTH), smem, st, p);
     KD_LAUNCH_CHECK("k_gemm");
+    return KD_OK;
+}
+
+// what one member of a grouped launch must be (launch_gemm_group checks the same, with messages):
+// a plain weight gradient the 256 x 256 v8 tile kernel takes -- MN-major x MN-major bf16 operands,
+// fp32 C, no bias / activation / residual / aux, the v8 loads' alignments
+bool gemm_group_member_ok(const kd_gemm_desc* d) {
+    return d && d->A && d->B && d->C && d->M >= 128 && d->N >= 128 && d->K > 0 &&
+           d->a_layout == KD_LAYOUT_MN_MAJOR && d->b_layout == KD_LAYOUT_MN_MAJOR && d->ab_dtype == KD_DTYPE_BF16 &&
+           d->c_dtype == KD_DTYPE_F32 && !d->bias && d->act == KD_ACT_NONE && !d->residual && !d->aux && !d->qkv &&
+           !d->row_stats && !d->alpha_dev && !d->b_pretiled && d->M % 8 == 0 && d->N % 8 == 0 && d->lda % 8 == 0 &&
+           d->ldb % 8 == 0 && d->ldc % 8 == 0 && d->lda >= d->M && d->ldb >= d->N && d->ldc >= d->N &&
+           (uintptr_t)d->A % 16 == 0 && (uintptr_t)d->B % 16 == 0 && (uintptr_t)d->C % 16 == 0 &&
+           (uint64_t)256 * d->lda * 2 < 0x7FFFFFFFull && (uint64_t)256 * d->ldb * 2 < 0x7FFFFFFFull;
+}
+
+int launch_gemm_group(const kd_gemm_desc* const* ds, int n, void* stream_) {
+    KD_CHECK_ARG(ds != nullptr, "gemm group: null member list");
+    KD_CHECK_ARG(n >= 1 && n <= GROUP_MAX, "gemm group: 1 to 4 members");
+    GemmGroupP g;
+    std::memset(&g, 0, sizeof(g));
+    int total = 0;
+    for (int i = 0; i < n; ++i) {
+        const kd_gemm_desc* d = ds[i];
+        KD_CHECK_ARG(d != nullptr, "gemm group: null member");
+        KD_CHECK_ARG(d->A && d->B && d->C, "gemm group: null operand");
+        KD_CHECK_ARG(d->M > 0 && d->N > 0 && d->K > 0, "gemm group: empty shape");
+        KD_CHECK_ARG(d->a_layout == KD_LAYOUT_MN_MAJOR && d->b_layout == KD_LAYOUT_MN_MAJOR,
+                     "gemm group: MN-major A and B only (weight gradients)");
+        KD_CHECK_ARG(d->ab_dtype == KD_DTYPE_BF16 && d->c_dtype == KD_DTYPE_F32, "gemm group: bf16 operands, fp32 C");
+        KD_CHECK_ARG(!d->bias && d->act == KD_ACT_NONE && !d->residual && !d->aux && !d->qkv && !d->row_stats &&
+                     !d->alpha_dev && !d->b_pretiled,
+                     "gemm group: no bias / activation / residual / aux / scatter / row statistics / device alpha");
+        KD_CHECK_ARG(d->M % 8 == 0 && d->N % 8 == 0, "gemm group: M % 8 == 0 and N % 8 == 0");
+        KD_CHECK_ARG(d->M >= 128 && d->N >= 128, "gemm group: M, N >= 128 (the 256 x 256 tile kernel)");
+        KD_CHECK_ARG(d->lda % 8 == 0 && d->ldb % 8 == 0 && d->ldc % 8 == 0 && d->lda >= d->M && d->ldb >= d->N &&
+                     d->ldc >= d->N, "gemm group: lda >= M, ldb >= N, ldc >= N, multiples of 8");
+        KD_CHECK_ARG((uintptr_t)d->A % 16 == 0 && (uintptr_t)d->B % 16 == 0 && (uintptr_t)d->C % 16 == 0,
+                     "gemm group: A, B and C must be 16-B aligned");
+        KD_CHECK_ARG((uint64_t)256 * d->lda * 2 < 0x7FFFFFFFull && (uint64_t)256 * d->ldb * 2 < 0x7FFFFFFFull,
+                     "gemm group: leading dimension too large for 31-bit buffer records");
+        GemmP& p = g.p[i];   // launch_gemm's parameters of this member on v8, unsplit
+        p.A = (const bf16*)d->A; p.B = (const bf16*)d->B; p.C = d->C;
+        p.lda = d->lda; p.ldb = d->ldb; p.ldc = d->ldc;
+        p.M = d->M; p.N = d->N; p.K = d->K; p.alpha = d->alpha;
+        p.c_f32 = 1; p.accumulate = d->accumulate;
+        p.kchunk = d->K; p.gy = 1; p.rst_inv_t = 1.f;
+        p.stagger = ab_knob("KD_GEMM_STAGGER", 1);
+        const int tiles_m = ceil_div(d->M, 256), tiles_n = ceil_div(d->N, 256);
+        p.gm = pick_gm(tiles_m, tiles_n);
+        p.gx = tiles_m * tiles_n;
+        g.t0[i] = total;
+        total += p.gx;
+    }
+    for (int i = n; i < GROUP_MAX; ++i) g.t0[i] = total;
+    hipLaunchKernelGGL(k_gemm8_group, dim3((unsigned)total), dim3(NTH8), (gemm2_lds<256, 256>()), as_stream(stream_), g);
+    KD_LAUNCH_CHECK("k_gemm8_group");
     return KD_OK;
 }
 

@@ -13,6 +13,13 @@ int launch_kd_student_stats(const void* student, int64_t ld_s, int V_s, int rows
                             void* stream);
 int kd_loss_check_impl(const void* ws, void* stream);
 int launch_gemm(const kd_gemm_desc* d, void* stream);
+// 1-4 weight-gradient GEMMs (MN-major x MN-major bf16 operands, fp32 C, no bias / activation /
+// residual) as one grid of 256 x 256 v8 tiles, each member unsplit over its whole K: no workspace,
+// no partial planes, no reduce launch; every member bit-identical to its own unsplit v8 launch.
+// A member that is not such a problem is KD_ERR_ARG and nothing is launched (gemm_group_member_ok
+// tells beforehand).  Internal: not an ABI symbol.
+int launch_gemm_group(const kd_gemm_desc* const* members, int n, void* stream);
+bool gemm_group_member_ok(const kd_gemm_desc* d);
 size_t gemm_workspace_size(const kd_gemm_desc* d);
 size_t gemm_pretile_size(int N, int K, int glu);
 int launch_gemm_pretile(const void* W, int64_t ldw, int N, int K, int glu, void* out, void* stream);
@@ -25,7 +32,8 @@ int launch_norm_fwd(int rms, const void* x, int64_t ldx, const void* w, const vo
 size_t norm_bwd_ws(int R, int D);
 int launch_norm_bwd(int rms, const void* x, int64_t ldx, const void* w, const void* dy, int64_t lddy, const float* mean,
                     const float* rstd, void* dx, int64_t lddx, int dx_accum, float* dw, float* db, int accum_w,
-                    void* ws, size_t ws_bytes, int R, int D, void* stream, int x_f32 = 0, int dy_group = 0);
+                    void* ws, size_t ws_bytes, int R, int D, void* stream, int x_f32 = 0, int dy_group = 0,
+                    const void* dx_in = nullptr);   // dx_accum: dx = dx_in + grad (nullptr: dx_in = dx, in place)
 int launch_qkv_split(const void* qkv, int64_t ld, void* q, void* k, void* v, const float* cos_t, const float* sin_t,
                      int B, int S, int nq, int nkv, int hd, int hdp, void* stream);
 int launch_qkv_merge(const float* dq, const void* dk, const void* dv, void* dqkv, int64_t ld, const float* cos_t,

@@ -214,7 +214,7 @@ template <bool RMS, int IT, typename XT, bool GDY = false>
 __global__ void __launch_bounds__(NT) k_norm_bwd(const XT* __restrict__ x, int64_t ldx, const bf16* __restrict__ w,
                                                  const void* __restrict__ dy, int64_t lddy,
                                                  const float* __restrict__ mean_in, const float* __restrict__ rstd_in,
-                                                 bf16* __restrict__ dx, int64_t lddx, int dx_accum,
+                                                 bf16* dx, const bf16* dx_in, int64_t lddx, int dx_accum,
                                                  float* __restrict__ dw_part, float* __restrict__ db_part,
                                                  int R, int D, int rows_per_block, int gP = 1, float gscale = 1.f) {
     extern __shared__ __attribute__((aligned(16))) float sacc[];  // [4 waves][2][D] per workgroup
@@ -239,7 +239,7 @@ __global__ void __launch_bounds__(NT) k_norm_bwd(const XT* __restrict__ x, int64
         const int row = min(row_, R - 1);
         const XT* xr = x + (int64_t)row * ldx;
         const char* gr = (const char*)dy + (GDY ? (int64_t)(row / gP) * lddy * 4 : (int64_t)row * lddy * 2);
-        const bf16* pr = dx + (int64_t)row * lddx;
+        const bf16* pr = dx_in + (int64_t)row * lddx;   // the incoming gradient (== dx when updated in place)
 #pragma unroll
         for (int it = 0; it < IT; ++it) {
             const int c = min(lane + it * 64, nch - 1);
@@ -973,8 +973,9 @@ size_t norm_bwd_ws(int R, int D) {
 
 int launch_norm_bwd(int rms, const void* x, int64_t ldx, const void* w, const void* dy, int64_t lddy, const float* mean,
                     const float* rstd, void* dx, int64_t lddx, int dx_accum, float* dw, float* db, int accum_w,
-                    void* ws, size_t ws_bytes, int R, int D, void* stream, int x_f32, int dy_group) {
+                    void* ws, size_t ws_bytes, int R, int D, void* stream, int x_f32, int dy_group, const void* dx_in) {
     KD_CHECK_ARG(x && w && dy && rstd && dx && (rms || mean), "norm_bwd: null pointer");
+    const bf16* dxi = dx_in ? (const bf16*)dx_in : (const bf16*)dx;   // the rows are read even when not accumulated
     KD_CHECK_ARG(dy_group == 0 || (!rms && dy_group > 0 && R % dy_group == 0 && (uintptr_t)dy % 16 == 0 && lddy % 4 == 0),
                  "norm_bwd: a grouped fp32 dy is for LayerNorm, rows a multiple of the group, 16-B rows");
     KD_CHECK_SHAPE(D % 8 == 0 && D <= 2048, "norm_bwd: D must be a multiple of 8, <= 2048");
@@ -990,21 +991,21 @@ int launch_norm_bwd(int rms, const void* x, int64_t ldx, const void* w, const vo
         if (dy_group && !RMSV) {                                                                                   \
             if (x_f32)                                                                                             \
                 hipLaunchKernelGGL((k_norm_bwd<false, ITV, float, true>), dim3(nb), dim3(NT), smem, st,              \
-                                   (const float*)x, ldx, (const bf16*)w, dy, lddy, mean, rstd, (bf16*)dx, lddx,       \
+                                   (const float*)x, ldx, (const bf16*)w, dy, lddy, mean, rstd, (bf16*)dx, dxi, lddx,       \
                                    dx_accum, dw ? dwp : nullptr, db ? dbp : nullptr, R, D, rows_per, dy_group,        \
                                    1.f / dy_group);                                                                 \
             else                                                                                                   \
                 hipLaunchKernelGGL((k_norm_bwd<false, ITV, bf16, true>), dim3(nb), dim3(NT), smem, st,               \
-                                   (const bf16*)x, ldx, (const bf16*)w, dy, lddy, mean, rstd, (bf16*)dx, lddx,        \
+                                   (const bf16*)x, ldx, (const bf16*)w, dy, lddy, mean, rstd, (bf16*)dx, dxi, lddx,        \
                                    dx_accum, dw ? dwp : nullptr, db ? dbp : nullptr, R, D, rows_per, dy_group,        \
                                    1.f / dy_group);                                                                 \
         } else if (x_f32)                                                                                          \
             hipLaunchKernelGGL((k_norm_bwd<RMSV, ITV, float>), dim3(nb), dim3(NT), smem, st, (const float*)x, ldx,   \
-                               (const bf16*)w, dy, lddy, mean, rstd, (bf16*)dx, lddx, dx_accum,                      \
+                               (const bf16*)w, dy, lddy, mean, rstd, (bf16*)dx, dxi, lddx, dx_accum,                      \
                                dw ? dwp : nullptr, (RMSV || !db) ? nullptr : dbp, R, D, rows_per);                 \
         else                                                                                                       \
             hipLaunchKernelGGL((k_norm_bwd<RMSV, ITV, bf16>), dim3(nb), dim3(NT), smem, st, (const bf16*)x, ldx,     \
-                               (const bf16*)w, dy, lddy, mean, rstd, (bf16*)dx, lddx, dx_accum,                      \
+                               (const bf16*)w, dy, lddy, mean, rstd, (bf16*)dx, dxi, lddx, dx_accum,                      \
                                dw ? dwp : nullptr, (RMSV || !db) ? nullptr : dbp, R, D, rows_per);                 \
     } while (0)
     const int it = (D + 511) / 512;

@@ -14,9 +14,12 @@
 // Weight gradients (dW = dY^T X and bias column sums) run on a second stream beside the
 // dgrad chain (dX = dY W), which is what the next layer waits for: the student's small-N
 // backward GEMMs (hidden 896, SigLIP 1152) leave CUs idle that the other stream fills.
-// The dgrad chain waits on the lane only before it updates dx in place (the lane reads
-// dx); every other buffer the lane reads is rewritten only after such a wait (see
-// lm_backward), so single buffers suffice.
+// A layer's weight gradients run as two grouped, unsplit launches (launch_gemm_group): alone
+// each fills a fraction of the CUs unless its K is split, and a split doubles its CU-time.
+// The residual gradient dx rotates through three buffers (a norm backward reads one and
+// writes the next), so the dgrad chain never waits for the lane to have read dx; it waits
+// for the previous layer's group only where it rewrites the single dgu / dqkv buffers that
+// group read, a whole layer later (see lm_backward).
 #include "common.h"
 #include "launchers.h"
 
@@ -60,6 +63,33 @@ int gemm_timed(const kd_gemm_desc* d, void* stream) {
     (void)hipEventCreate(&r.e1);
     (void)hipEventRecord(r.e0, as_stream(stream));
     const int st = launch_gemm(d, stream);
+    (void)hipEventRecord(r.e1, as_stream(stream));
+    std::lock_guard<std::mutex> g(g_timer_mu);
+    g_timer.push_back(r);
+    return st;
+}
+
+// A grouped weight-gradient launch (launch_gemm_group) through the timer: one record per group, keyed
+// as its largest member with the suffix :g<members>, flops summed over the members (so the gemm_nn
+// family's totals stay right and a reader sees from the suffix that the grouped path ran)
+int gemm_group_timed(const kd_gemm_desc* const* ds, int n, void* stream) {
+    if (!g_timer_on) return launch_gemm_group(ds, n, stream);
+    TimerRec r;
+    r.flops = 0;
+    const kd_gemm_desc* big = nullptr;
+    for (int i = 0; i < n && ds; ++i) {
+        if (!ds[i]) continue;
+        const double f = 2.0 * ds[i]->M * ds[i]->N * ds[i]->K;
+        if (!big || f > 2.0 * big->M * big->N * big->K) big = ds[i];
+        r.flops += f;
+    }
+    if (!big) return launch_gemm_group(ds, n, stream);   // rejected there
+    r.key = "gemm_nn:" + std::to_string(big->M) + "x" + std::to_string(big->N) + "x" + std::to_string(big->K) + ":f32" +
+            (big->accumulate ? ":acc" : "") + ":g" + std::to_string(n);
+    (void)hipEventCreate(&r.e0);
+    (void)hipEventCreate(&r.e1);
+    (void)hipEventRecord(r.e0, as_stream(stream));
+    const int st = launch_gemm_group(ds, n, stream);
     (void)hipEventRecord(r.e1, as_stream(stream));
     std::lock_guard<std::mutex> g(g_timer_mu);
     g_timer.push_back(r);
@@ -191,6 +221,10 @@ struct kd_model {
     float* g = nullptr;
     int train_vision = 0, train_projector = 0, train_language = 0;
     int lane_split_k = 0;     // split-K of the lane's GEMMs (KD_WGRAD_SPLIT_K; 0 = cost model)
+    // a layer's weight gradients as grouped, unsplit launches (launch_gemm_group; KD_WGRAD_GROUP=0:
+    // one planned kd_gemm each), and (A/B, with grouping off) KD_WGRAD_V8_UNSPLIT=1: each of them
+    // alone on the group's kernel -- v8 tiles, unsplit, one launch per GEMM, the group's bits
+    int lane_group = 1, lane_v8_unsplit = 0;
     // fp32 residual streams (kd_model_set_residual_f32): the SigLIP / Qwen2 hidden state x that
     // every layer adds into is kept in fp32 (GEMM epilogues add the residual in fp32 and write
     // fp32; the norms read fp32) instead of being rounded to bf16 after every add
@@ -338,6 +372,61 @@ struct Lane {
     }
     int colsum(const void* dy, int64_t ld, int M, int N, float* out) {
         return launch_colsum(dy, ld, M, N, out, 1, lane);
+    }
+    // ---- a layer's weight gradients, grouped (kd_model::lane_group) ----
+    // member() / member_colsum() stand where the per-GEMM lane launches a weight gradient and its
+    // bias column sum; with grouping on they only join the pending group, and flush() -- placed
+    // where the group's last operand has been written -- launches the members as ONE unsplit
+    // grouped GEMM and then the column sums.  With grouping off they launch at once, as the
+    // per-GEMM lane does.  Either way flush() returns the event after the group's last read.
+    struct Colsum { const void* dy; int64_t ld; int M, N; float* out; };
+    kd_gemm_desc pend[4];
+    Colsum pend_cs[4];
+    int npend = 0, ncs = 0;
+    int member(int M, int Nout, int Kin, const void* dy, int64_t lddy, const void* x, int64_t ldx, float* dW) {
+        kd_gemm_desc d;
+        std::memset(&d, 0, sizeof(d));
+        d.M = Nout; d.N = Kin; d.K = M;
+        d.a_layout = d.b_layout = KD_LAYOUT_MN_MAJOR;
+        d.A = dy; d.lda = lddy; d.B = x; d.ldb = ldx;
+        d.C = dW; d.ldc = Kin;
+        d.c_dtype = KD_DTYPE_F32; d.accumulate = 1; d.alpha = 1.f;
+        const bool ok = gemm_group_member_ok(&d);
+        if (m->lane_group && ok && npend < 4) {
+            pend[npend++] = d;
+            return KD_OK;
+        }
+        begin();
+        if (!m->lane_group && m->lane_v8_unsplit && ok) {
+            const kd_gemm_desc* one = &d;
+            return gemm_group_timed(&one, 1, lane);
+        }
+        return wgrad(M, Nout, Kin, dy, lddy, x, ldx, dW);
+    }
+    int member_colsum(const void* dy, int64_t ld, int M, int N, float* out) {
+        if (m->lane_group && ncs < 4) {
+            pend_cs[ncs++] = Colsum{dy, ld, M, N, out};
+            return KD_OK;
+        }
+        return colsum(dy, ld, M, N, out);   // after its member(): the lane has joined the chain
+    }
+    int flush(hipEvent_t* ev) {
+        if (npend || ncs) begin();
+        if (npend) {
+            const kd_gemm_desc* ds[4];
+            for (int i = 0; i < npend; ++i) ds[i] = &pend[i];
+            const int n = npend;
+            npend = 0;
+            KD_TRY(gemm_group_timed(ds, n, lane));
+        }
+        for (int i = 0; i < ncs; ++i) {
+            const Colsum& c = pend_cs[i];
+            const int st = colsum(c.dy, c.ld, c.M, c.N, c.out);
+            if (st != KD_OK) { ncs = 0; return st; }
+        }
+        ncs = 0;
+        *ev = end();
+        return KD_OK;
     }
 };
 inline void wait(hipStream_t s, hipEvent_t e) {
@@ -670,7 +759,11 @@ int lm_forward(kd_model* m, const FwdPlan& P, const float* cs, const float* sn, 
 
 // ---------------------------------------------------------- backward plan ----
 struct BwdPlan {
-    bf16 *dx, *da, *dgu, *dh2, *do_, *dk, *dv, *dqkv, *dh, *demb;   // language model
+    bf16 *dx, *da, *dgu, *dh2, *do_, *dk, *dv, *dqkv, *dh;   // language model
+    // the residual gradient rotates through three buffers (each norm backward reads one and writes
+    // the next), so a lane read of one version has to finish only before its buffer comes round
+    // again, two norm backwards later; dx3[0] == dx, dxv3[0] == dxv
+    bf16 *dx3[3], *dxv3[3];
     float *dq, *delta;
     bf16 *dfeats, *dz, *dxv, *du, *dh2v, *dov, *dqkvv, *dhv;   // projector / vision (attention writes dqkvv directly)
     float *deltav;
@@ -705,6 +798,9 @@ BwdPlan plan_backward(const kd_model* m, int B, int L, int n_tiles, void* base) 
     const int64_t NT = (int64_t)NI * np, D = c.v_hidden, Iv = c.v_inter, hdp = C.v_hdp();
     const int64_t M = (int64_t)B * L, H = c.t_hidden, TI = c.t_inter, qd = C.qd(), kvd = C.kvd();
     P.dx = A.take<bf16>(M * H);
+    P.dx3[0] = P.dx;
+    P.dx3[1] = A.take<bf16>(M * H);
+    P.dx3[2] = A.take<bf16>(M * H);
     P.da = A.take<bf16>(M * TI);
     P.dgu = A.take<bf16>(M * 2 * TI);
     P.dh2 = A.take<bf16>(M * H);
@@ -720,13 +816,15 @@ BwdPlan plan_backward(const kd_model* m, int B, int L, int n_tiles, void* base) 
     P.delta = A.take<float>((int64_t)B * c.t_heads * L);
     P.dqkv = A.take<bf16>(M * (qd + 2 * kvd));
     P.dh = A.take<bf16>(M * H);
-    P.demb = P.dx;   // the LM backward's dx is d(inputs_embeds)
     kd_attn_bwd_desc ad = lm_attn_desc(m, B, L);
     P.attn_ws_bytes = attn_bwd_workspace_size(&ad);
     P.attn_ws = P.attn_ws_bytes ? A.take<char>(P.attn_ws_bytes) : nullptr;
     P.dfeats = A.take<bf16>(NT * H);
     P.dz = A.take<bf16>(NT * H);
     P.dxv = A.take<bf16>(NT * D);
+    P.dxv3[0] = P.dxv;
+    P.dxv3[1] = A.take<bf16>(NT * D);
+    P.dxv3[2] = A.take<bf16>(NT * D);
     P.du = A.take<bf16>(NT * Iv);
     P.dh2v = A.take<bf16>(NT * D);
     P.dov = A.take<bf16>(NT * D);
@@ -753,50 +851,54 @@ BwdPlan plan_backward(const kd_model* m, int B, int L, int n_tiles, void* base) 
 
 // ----------------------------------------------------------------- backward ----
 int lm_backward(kd_model* m, const FwdPlan& F, const BwdPlan& P, const float* cs, const float* sn, int B, int L,
-                const void* dhn, Lane& lane, hipStream_t s, kd_layer_cb cb, void* user) {
+                const void* dhn, Lane& lane, hipStream_t s, kd_layer_cb cb, void* user, const bf16** demb) {
     const kd_model_config& c = m->C.c;
     const int M = B * L, H = c.t_hidden, TI = c.t_inter, qd = m->C.qd(), kvd = m->C.kvd(), hd = c.t_head_dim;
     const bool gw = m->train_language != 0;
     const int f32 = m->rf32_t;
-    KD_TRY(launch_norm_bwd(1, F.x_lm_last, H, m->W(m->i_norm), dhn, H, nullptr, F.rf, P.dx, H, 0,
+    // dx rotates through P.dx3: a norm backward reads dx and writes the next buffer, so the lane's
+    // read of a dx version must be over only two norm backwards later.  The lane's two groups per
+    // layer read: A (down, gate|up) dx, dgu and the saved a / h2; B (o, q|k|v) the next dx, dqkv and
+    // the saved o / h.  dgu and dqkv are single buffers, rewritten one layer later by that layer's
+    // first GEMM / attention backward, which therefore wait for the previous layer's group -- the
+    // same waits cover the dx buffer that comes round again right after them.
+    int cur = 0;
+    bf16* dx = P.dx3[0];
+    auto rotate = [&] { cur = (cur + 1) % 3; return P.dx3[cur]; };
+    hipEvent_t evA = nullptr, evB = nullptr;   // the previous layer's groups
+    KD_TRY(launch_norm_bwd(1, F.x_lm_last, H, m->W(m->i_norm), dhn, H, nullptr, F.rf, dx, H, 0,
                            gw ? m->G(m->i_norm) : nullptr, nullptr, 1, P.norm_ws, P.norm_ws_bytes, M, H, s, f32));
     for (int i = c.t_layers - 1; i >= 0; --i) {
         const LmLayerBufs& b = F.ll[i];
         GemmArgs g0;
+        wait(s, evA);   // dgu is rewritten next (the previous layer's group A read it)
         // MLP: dgu = swiglu'(gu) (dx Wdown) -- one GEMM with the KD_ACT_DSWIGLU epilogue where the
         // tiled kernels run it, else the GEMM + k_swiglu_bwd (same bits) ; dh2 = dgu [Wgate; Wup]
         if (fused_dact_ok(M, TI)) {
             GemmArgs gs;
             gs.act = KD_ACT_DSWIGLU; gs.aux = b.gu; gs.ld_aux = 2 * TI; gs.split_k = 1;
-            KD_TRY(gemm(s, P.splitk_main, M, TI, H, km(P.dx, H), mn(m->W(m->lm(i, LDW)), TI), P.dgu, 2 * TI, gs));
+            KD_TRY(gemm(s, P.splitk_main, M, TI, H, km(dx, H), mn(m->W(m->lm(i, LDW)), TI), P.dgu, 2 * TI, gs));
         } else {
-            KD_TRY(gemm(s, P.splitk_main, M, TI, H, km(P.dx, H), mn(m->W(m->lm(i, LDW)), TI), P.da, TI, g0));
+            KD_TRY(gemm(s, P.splitk_main, M, TI, H, km(dx, H), mn(m->W(m->lm(i, LDW)), TI), P.da, TI, g0));
+            KD_TRY(launch_swiglu_bwd(b.gu, 2 * TI, P.da, TI, P.dgu, 2 * TI, M, TI, s));
         }
-        hipEvent_t ev = nullptr;
-        if (gw) {
-            lane.begin();
-            KD_TRY(lane.wgrad(M, H, TI, P.dx, H, b.a, TI, m->G(m->lm(i, LDW))));
-            ev = lane.end();
+        if (gw) {   // group A, as soon as dgu is written
+            KD_TRY(lane.member(M, H, TI, dx, H, b.a, TI, m->G(m->lm(i, LDW))));
+            KD_TRY(lane.member(M, 2 * TI, H, P.dgu, 2 * TI, b.h2, H, m->G(m->lm(i, LGW))));
+            KD_TRY(lane.flush(&evA));
         }
-        if (!fused_dact_ok(M, TI)) KD_TRY(launch_swiglu_bwd(b.gu, 2 * TI, P.da, TI, P.dgu, 2 * TI, M, TI, s));
         KD_TRY(gemm(s, P.splitk_main, M, H, 2 * TI, km(P.dgu, 2 * TI), mn(m->W(m->lm(i, LGW)), H), P.dh2, H, g0));
-        if (gw) {
-            lane.begin();
-            KD_TRY(lane.wgrad(M, 2 * TI, H, P.dgu, 2 * TI, b.h2, H, m->G(m->lm(i, LGW))));
-            lane.end();
+        {
+            bf16* dx_in = dx;
+            dx = rotate();
+            KD_TRY(launch_norm_bwd(1, b.x_mid, H, m->W(m->lm(i, LPOSTW)), P.dh2, H, nullptr, b.r2, dx, H, 1,
+                                   gw ? m->G(m->lm(i, LPOSTW)) : nullptr, nullptr, 1, P.norm_ws, P.norm_ws_bytes, M, H,
+                                   s, f32, 0, dx_in));
         }
-        wait(s, ev);   // dx is updated in place next (the lane read it)
-        KD_TRY(launch_norm_bwd(1, b.x_mid, H, m->W(m->lm(i, LPOSTW)), P.dh2, H, nullptr, b.r2, P.dx, H, 1,
-                               gw ? m->G(m->lm(i, LPOSTW)) : nullptr, nullptr, 1, P.norm_ws, P.norm_ws_bytes, M, H, s,
-                               f32));
         // attention: do = dx Wo ; flash backward ; dqkv (RoPE undone) ; dh = dqkv Wqkv
-        KD_TRY(gemm(s, P.splitk_main, M, qd, H, km(P.dx, H), mn(m->W(m->lm(i, LOW)), qd), P.do_, qd, g0));
-        ev = nullptr;
-        if (gw) {
-            lane.begin();
-            KD_TRY(lane.wgrad(M, H, qd, P.dx, H, b.o, qd, m->G(m->lm(i, LOW))));
-            ev = lane.end();
-        }
+        KD_TRY(gemm(s, P.splitk_main, M, qd, H, km(dx, H), mn(m->W(m->lm(i, LOW)), qd), P.do_, qd, g0));
+        if (gw) KD_TRY(lane.member(M, H, qd, dx, H, b.o, qd, m->G(m->lm(i, LOW))));
+        wait(s, evB);   // dqkv is rewritten next (the previous layer's group B read it)
         {
             kd_attn_bwd_desc d = lm_attn_desc(m, B, L);
             d.q = b.q; d.k = b.k; d.v = b.v; d.o = b.o; d.dO = P.do_; d.lse = b.lse; d.delta = P.delta;
@@ -807,20 +909,23 @@ int lm_backward(kd_model* m, const FwdPlan& F, const BwdPlan& P, const float* cs
         }
         if (P.dq)
             KD_TRY(launch_qkv_merge(P.dq, P.dk, P.dv, P.dqkv, qd + 2 * kvd, cs, sn, B, L, c.t_heads, c.t_kv_heads, hd, hd, s));
+        if (gw) {   // group B, as soon as dqkv is written
+            KD_TRY(lane.member(M, qd + 2 * kvd, H, P.dqkv, qd + 2 * kvd, b.h, H, m->G(m->lm(i, LQW))));
+            KD_TRY(lane.member_colsum(P.dqkv, qd + 2 * kvd, M, qd + 2 * kvd, m->G(m->lm(i, LQB))));
+            KD_TRY(lane.flush(&evB));
+        }
         KD_TRY(gemm(s, P.splitk_main, M, H, qd + 2 * kvd, km(P.dqkv, qd + 2 * kvd), mn(m->W(m->lm(i, LQW)), H), P.dh, H,
                     g0));
-        if (gw) {
-            lane.begin();
-            KD_TRY(lane.wgrad(M, qd + 2 * kvd, H, P.dqkv, qd + 2 * kvd, b.h, H, m->G(m->lm(i, LQW))));
-            KD_TRY(lane.colsum(P.dqkv, qd + 2 * kvd, M, qd + 2 * kvd, m->G(m->lm(i, LQB))));
-            lane.end();
+        {
+            bf16* dx_in = dx;
+            dx = rotate();
+            KD_TRY(launch_norm_bwd(1, b.x, H, m->W(m->lm(i, LINW)), P.dh, H, nullptr, b.r1, dx, H, 1,
+                                   gw ? m->G(m->lm(i, LINW)) : nullptr, nullptr, 1, P.norm_ws, P.norm_ws_bytes, M, H, s,
+                                   f32, 0, dx_in));
         }
-        wait(s, ev);
-        KD_TRY(launch_norm_bwd(1, b.x, H, m->W(m->lm(i, LINW)), P.dh, H, nullptr, b.r1, P.dx, H, 1,
-                               gw ? m->G(m->lm(i, LINW)) : nullptr, nullptr, 1, P.norm_ws, P.norm_ws_bytes, M, H, s,
-                               f32));
         if (cb) cb(user, i);
     }
+    *demb = dx;   // the LM backward's dx is d(inputs_embeds)
     return KD_OK;
 }
 
@@ -831,7 +936,12 @@ int vision_backward(kd_model* m, const FwdPlan& F, const BwdPlan& P, int NI, con
     const int np = C.np(), D = c.v_hidden, Iv = c.v_inter, hdp = C.v_hdp(), hd = C.v_hd();
     const int NT = NI * np;
     const bool gw = m->train_vision != 0;
-    bf16* dx = P.dxv;
+    // dx rotates through P.dxv3 and the lane's groups A (fc2, fc1) and B (out_proj, q|k|v) are
+    // ordered against the single du / dqkvv buffers exactly as in lm_backward
+    int cur = 0;
+    bf16* dx = P.dxv3[0];
+    auto rotate = [&] { cur = (cur + 1) % 3; return P.dxv3[cur]; };
+    hipEvent_t evA = nullptr, evB = nullptr;   // the previous layer's groups
     const int f32 = m->rf32_v;
     if (dpost)
         KD_TRY(launch_norm_bwd(0, F.x_vis_last, D, m->W(m->i_post_w), dpost, D, F.pm, F.pr, dx, D, 1,
@@ -841,40 +951,36 @@ int vision_backward(kd_model* m, const FwdPlan& F, const BwdPlan& P, int NI, con
     for (int i = c.v_layers - 1; i >= 0; --i) {
         const VisLayerBufs& b = F.vl[i];
         const bool fuse_gelu = fused_dact_ok(NT, Iv);
+        wait(s, evA);   // du is rewritten next (the previous layer's group A read it)
         if (fuse_gelu) {   // du = gelu'(pre) (dx Wfc2) in one GEMM (KD_ACT_DGELU_TANH epilogue)
             GemmArgs gd;
             gd.act = KD_ACT_DGELU_TANH; gd.aux = b.pre; gd.ld_aux = Iv; gd.split_k = 1;
             KD_TRY(gemm(s, P.splitk_main, NT, Iv, D, km(dx, D), mn(m->W(m->vis(i, VFC2W)), Iv), P.du, Iv, gd));
         } else {
             KD_TRY(gemm(s, P.splitk_main, NT, Iv, D, km(dx, D), mn(m->W(m->vis(i, VFC2W)), Iv), P.du, Iv, g0));
+            KD_TRY(launch_act_bwd(b.pre, P.du, P.du, (int64_t)NT * Iv, KD_ACT_GELU_TANH, s));   // dpre in place
         }
-        hipEvent_t ev = nullptr;
-        if (gw) {
-            lane.begin();
-            KD_TRY(lane.wgrad(NT, D, Iv, dx, D, b.u, Iv, m->G(m->vis(i, VFC2W))));
-            KD_TRY(lane.colsum(dx, D, NT, D, m->G(m->vis(i, VFC2B))));
-            ev = lane.end();
+        if (gw) {   // group A, as soon as du is written
+            KD_TRY(lane.member(NT, D, Iv, dx, D, b.u, Iv, m->G(m->vis(i, VFC2W))));
+            KD_TRY(lane.member_colsum(dx, D, NT, D, m->G(m->vis(i, VFC2B))));
+            KD_TRY(lane.member(NT, Iv, D, P.du, Iv, b.h2, D, m->G(m->vis(i, VFC1W))));
+            KD_TRY(lane.member_colsum(P.du, Iv, NT, Iv, m->G(m->vis(i, VFC1B))));
+            KD_TRY(lane.flush(&evA));
         }
-        if (!fuse_gelu) KD_TRY(launch_act_bwd(b.pre, P.du, P.du, (int64_t)NT * Iv, KD_ACT_GELU_TANH, s));   // dpre in place
         KD_TRY(gemm(s, P.splitk_main, NT, D, Iv, km(P.du, Iv), mn(m->W(m->vis(i, VFC1W)), D), P.dh2v, D, g0));
-        if (gw) {
-            lane.begin();
-            KD_TRY(lane.wgrad(NT, Iv, D, P.du, Iv, b.h2, D, m->G(m->vis(i, VFC1W))));
-            KD_TRY(lane.colsum(P.du, Iv, NT, Iv, m->G(m->vis(i, VFC1B))));
-            lane.end();
+        {
+            bf16* dx_in = dx;
+            dx = rotate();
+            KD_TRY(launch_norm_bwd(0, b.x_mid, D, m->W(m->vis(i, VLN2W)), P.dh2v, D, b.m2, b.r2, dx, D, 1,
+                                   gw ? m->G(m->vis(i, VLN2W)) : nullptr, gw ? m->G(m->vis(i, VLN2B)) : nullptr, 1,
+                                   P.norm_ws, P.norm_ws_bytes, NT, D, s, f32, 0, dx_in));
         }
-        wait(s, ev);
-        KD_TRY(launch_norm_bwd(0, b.x_mid, D, m->W(m->vis(i, VLN2W)), P.dh2v, D, b.m2, b.r2, dx, D, 1,
-                               gw ? m->G(m->vis(i, VLN2W)) : nullptr, gw ? m->G(m->vis(i, VLN2B)) : nullptr, 1, P.norm_ws,
-                               P.norm_ws_bytes, NT, D, s, f32));
         KD_TRY(gemm(s, P.splitk_main, NT, D, D, km(dx, D), mn(m->W(m->vis(i, VOW)), D), P.dov, D, g0));
-        ev = nullptr;
         if (gw) {
-            lane.begin();
-            KD_TRY(lane.wgrad(NT, D, D, dx, D, b.o, D, m->G(m->vis(i, VOW))));
-            KD_TRY(lane.colsum(dx, D, NT, D, m->G(m->vis(i, VOB))));
-            ev = lane.end();
+            KD_TRY(lane.member(NT, D, D, dx, D, b.o, D, m->G(m->vis(i, VOW))));
+            KD_TRY(lane.member_colsum(dx, D, NT, D, m->G(m->vis(i, VOB))));
         }
+        wait(s, evB);   // dqkvv is rewritten next (the previous layer's group B read it)
         {
             kd_attn_bwd_desc d = vis_attn_desc(m, NI);
             d.q = b.q; d.k = b.k; d.v = b.v; d.o = b.o; d.dO = P.dov; d.lse = b.lse; d.delta = P.deltav;
@@ -887,17 +993,19 @@ int vision_backward(kd_model* m, const FwdPlan& F, const BwdPlan& P, int NI, con
         if (P.dqv)
             KD_TRY(launch_qkv_merge(P.dqv, P.dkv, P.dvv, P.dqkvv, 3 * D, nullptr, nullptr, NI, np, c.v_heads, c.v_heads,
                                     hd, hdp, s));
-        KD_TRY(gemm(s, P.splitk_main, NT, D, 3 * D, km(P.dqkvv, 3 * D), mn(m->W(m->vis(i, VQW)), D), P.dhv, D, g0));
-        if (gw) {
-            lane.begin();
-            KD_TRY(lane.wgrad(NT, 3 * D, D, P.dqkvv, 3 * D, b.h, D, m->G(m->vis(i, VQW))));
-            KD_TRY(lane.colsum(P.dqkvv, 3 * D, NT, 3 * D, m->G(m->vis(i, VQB))));
-            lane.end();
+        if (gw) {   // group B, as soon as dqkvv is written
+            KD_TRY(lane.member(NT, 3 * D, D, P.dqkvv, 3 * D, b.h, D, m->G(m->vis(i, VQW))));
+            KD_TRY(lane.member_colsum(P.dqkvv, 3 * D, NT, 3 * D, m->G(m->vis(i, VQB))));
+            KD_TRY(lane.flush(&evB));
         }
-        wait(s, ev);
-        KD_TRY(launch_norm_bwd(0, b.x, D, m->W(m->vis(i, VLN1W)), P.dhv, D, b.m1, b.r1, dx, D, 1,
-                               gw ? m->G(m->vis(i, VLN1W)) : nullptr, gw ? m->G(m->vis(i, VLN1B)) : nullptr, 1, P.norm_ws,
-                               P.norm_ws_bytes, NT, D, s, f32));
+        KD_TRY(gemm(s, P.splitk_main, NT, D, 3 * D, km(P.dqkvv, 3 * D), mn(m->W(m->vis(i, VQW)), D), P.dhv, D, g0));
+        {
+            bf16* dx_in = dx;
+            dx = rotate();
+            KD_TRY(launch_norm_bwd(0, b.x, D, m->W(m->vis(i, VLN1W)), P.dhv, D, b.m1, b.r1, dx, D, 1,
+                                   gw ? m->G(m->vis(i, VLN1W)) : nullptr, gw ? m->G(m->vis(i, VLN1B)) : nullptr, 1,
+                                   P.norm_ws, P.norm_ws_bytes, NT, D, s, f32, 0, dx_in));
+        }
         // layer i's gradients (and post_layernorm's) are enqueued: the caller may all-reduce them
         // while the layers below run (ABI 9; the weight gradients are on the lane, which the
         // callback joins before it launches a collective)
@@ -1052,6 +1160,8 @@ int kd_model_create(const kd_model_config* cfg, const void* weights, float* grad
     const int on = grad ? 1 : 0;
     m->train_vision = m->train_projector = m->train_language = on;
     m->lane_split_k = kd::ab_knob("KD_WGRAD_SPLIT_K", 0);
+    m->lane_group = kd::ab_knob("KD_WGRAD_GROUP", 1) != 0;
+    m->lane_v8_unsplit = kd::ab_knob("KD_WGRAD_V8_UNSPLIT", 0) != 0;
     m->i_post_w = m->i_vis0 + cfg->v_layers * kd::VNF;
     m->i_post_b = m->i_post_w + 1;
     m->i_p1w = m->i_post_b + 1;
@@ -1223,10 +1333,11 @@ int kd_model_backward(kd_model* m, const void* fwd_workspace, const int64_t* ids
     hipEvent_t entry = m->event();
     (void)hipEventRecord(entry, lane.lane);
     const int NI = n_tiles, NT = NI * m->C.np(), M = B * L, H = c.t_hidden, D = c.v_hidden;
-    KD_TRY(lm_backward(m, F, P, rope_cos, rope_sin, B, L, dhn, lane, s, on_layer_done, user));
+    const bf16* demb = nullptr;
+    KD_TRY(lm_backward(m, F, P, rope_cos, rope_sin, B, L, dhn, lane, s, on_layer_done, user, &demb));
     wait(s, entry);
     const bool need_vision = m->train_vision != 0;
-    KD_TRY(launch_embed_bwd(ids, src, P.demb, m->train_language ? m->G(m->i_embed) : nullptr, P.dfeats,
+    KD_TRY(launch_embed_bwd(ids, src, demb, m->train_language ? m->G(m->i_embed) : nullptr, P.dfeats,
                             m->train_projector ? m->G(m->i_newline) : nullptr, M, H, s));
     {   // projector backward
         GemmArgs g0;
