@@ -488,7 +488,22 @@ int kd_rope_row(const float* cos_table, const float* sin_table, int hh, const in
  *   workspace >= nb * V bytes.
  * kd_rope_rows: cos/sin row of position cur_dev[b] - 1 of the [table_rows, hh] tables into row b
  *   of [nb, hh] buffers: as kd_qkv_split's tables with (B = 1, S = nb) they rotate token b by its
- *   own position (nb <= KD_GEMV_ROWS_MAX: the grouped prefill below rotates all its rows at once). */
+ *   own position (nb <= KD_GEMV_ROWS_MAX: the grouped prefill below rotates all its rows at once).
+ * kd_gen_finish: which rows have emitted an end-of-sequence token, kept on the device so that the
+ *   decode loop can stop once all have (one int32 read every few steps instead of one per token).
+ *   tok [nb] int64: the tokens just chosen (`out` of kd_gen_select / kd_gen_select_batch); cur_dev
+ *   [nb]: the rows' lengths after that select (the new token counted); eos_ids_host: n_eos ids
+ *   (1..KD_GEN_EOS_MAX) in HOST memory, copied into the kernel's arguments by value, so a captured
+ *   step replays with fixed arguments and no device buffer of ids exists.  For each row b with
+ *   fin[b] == 0 whose tok[b] equals one of the ids (compared as int64), fin[b] = cur_dev[b]; a
+ *   non-zero fin[b] is never changed again; then live[0] = the number of rows with fin[b] == 0.
+ *   Nothing else is written.  fin [nb] and live [1] are device int32; the caller zeroes fin before
+ *   the first call of a sequence.  1 <= nb <= 64 (one wave, lane b owns row b; the count is a
+ *   ballot, no atomics): bit-deterministic.  Null pointers -> KD_ERR_ARG, nb or n_eos out of range
+ *   -> KD_ERR_SHAPE, both before any device work. */
+#define KD_GEN_EOS_MAX 8
+int kd_gen_finish(const int64_t* tok, const int32_t* cur_dev, int nb, const int64_t* eos_ids_host, int n_eos,
+                  int32_t* fin, int32_t* live, void* stream);
 size_t kd_gemv_batch_workspace_size(int N, int K, int epilogue);
 int kd_gemv_batch(const void* x, int64_t ldx, int nb, const void* W, int64_t ldw, const void* extra, void* y, int N,
                   int K, int epilogue, int inter, const void* norm_w, float eps, void* workspace,

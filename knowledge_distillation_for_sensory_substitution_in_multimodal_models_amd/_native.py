@@ -129,6 +129,7 @@ _vp, _i32, _i64, _sz, _f32 = C.c_void_p, C.c_int, C.c_int64, C.c_size_t, C.c_flo
 
 # name -> (restype, argtypes).  Kept in the same order as include/kdstep.h.
 KD_GEMV_ROWS_MAX = 1024   # include/kdstep.h: rows per kd_gemv_rows / kd_attn_extend call
+KD_GEN_EOS_MAX = 8        # include/kdstep.h: EOS ids per kd_gen_finish call
 
 SIGNATURES = {
     "kd_abi_version": (_i32, []),
@@ -188,6 +189,7 @@ SIGNATURES = {
                                     _vp]),
     "kd_gen_select_batch": (_i32, [_vp, _i64, _i32, _vp, _i32, _i32, _vp, _f32, _i32, _vp, _sz, _vp, _vp]),
     "kd_rope_rows": (_i32, [_vp, _vp, _i32, _i32, _i32, _vp, _vp, _vp, _vp]),
+    "kd_gen_finish": (_i32, [_vp, _vp, _i32, _vp, _i32, _vp, _vp, _vp]),
     "kd_gemv_rows_workspace_size": (_sz, [_i32, _i32, _i32, _i32]),
     "kd_gemv_rows": (_i32, [_vp, _i64, _i32, _vp, _i64, _vp, _vp, _i32, _i32, _i32, _i32, _vp, _f32, _vp, _sz, _vp]),
     "kd_attn_extend_workspace_size": (_sz, [_i32, _i32, _i32, _i32]),

@@ -179,6 +179,10 @@ int kd_rope_rows(const float* c, const float* sn, int hh, int rows, int nb, cons
                  void* s) {
     return kd::launch_rope_rows(c, sn, hh, rows, nb, cur, cr, sr, s);
 }
+int kd_gen_finish(const int64_t* tok, const int32_t* cur, int nb, const int64_t* eos_ids_host, int n_eos, int32_t* fin,
+                  int32_t* live, void* s) {
+    return kd::launch_gen_finish(tok, cur, nb, eos_ids_host, n_eos, fin, live, s);
+}
 size_t kd_gemv_rows_workspace_size(int rows, int N, int K, int epi) { return kd::gemv_rows_ws(rows, N, K, epi); }
 int kd_gemv_rows(const void* x, int64_t ldx, int rows, const void* W, int64_t ldw, const void* extra, void* y, int N,
                  int K, int epi, int I, const void* norm_w, float eps, void* ws, size_t wsb, void* s) {

@@ -665,6 +665,36 @@ __global__ void k_rope_rows(const float* __restrict__ cos_t, const float* __rest
     }
 }
 
+// The EOS ids of kd_gen_finish, passed by value: a captured step replays with fixed arguments.
+struct GenEos {
+    int64_t id[KD_GEN_EOS_MAX];
+    int n;
+};
+
+// One wave, lane b < nb owns row b: fin[b] latches the row's length at its first EOS token
+// (compared as int64), live[0] = rows still at 0 (ballot + popcount; no atomics).
+__global__ void __launch_bounds__(64) k_gen_finish(const int64_t* __restrict__ tok, const int* __restrict__ cur_dev,
+                                                   int nb, GenEos eos, int* __restrict__ fin, int* __restrict__ live) {
+    const int b = threadIdx.x;
+    bool open = false;
+    if (b < nb) {
+        int f = fin[b];
+        if (f == 0) {
+            const int64_t t = tok[b];
+            bool hit = false;
+#pragma unroll
+            for (int e = 0; e < KD_GEN_EOS_MAX; ++e) hit |= e < eos.n && t == eos.id[e];
+            if (hit) {
+                f = cur_dev[b];
+                fin[b] = f;
+            }
+        }
+        open = f == 0;
+    }
+    const unsigned long long m = __ballot(open);
+    if (b == 0) live[0] = __popcll(m);
+}
+
 
 // ------------------------------------------- grouped prefill: the suffix rows of a chunk ----
 // k_gemv_batch for rows > 16 (kd_gemv_rows): the workgroup of a wave_n = 0 plan loads its wave's
@@ -1176,6 +1206,19 @@ int launch_rope_rows(const float* cos_t, const float* sin_t, int hh, int rows, i
     hipLaunchKernelGGL(k_rope_rows, dim3(nb), dim3(256), 0, as_stream(stream), cos_t, sin_t, hh, rows, cur_dev, cos_rows,
                        sin_rows);
     KD_LAUNCH_CHECK("k_rope_rows");
+    return KD_OK;
+}
+
+int launch_gen_finish(const int64_t* tok, const int* cur_dev, int nb, const int64_t* eos_ids_host, int n_eos, int* fin,
+                      int* live, void* stream) {
+    KD_CHECK_ARG(tok && cur_dev && eos_ids_host && fin && live, "gen_finish: null pointer");
+    KD_CHECK_SHAPE(nb >= 1 && nb <= 64, "gen_finish: 1 <= nb <= 64");
+    KD_CHECK_SHAPE(n_eos >= 1 && n_eos <= KD_GEN_EOS_MAX, "gen_finish: 1 <= n_eos <= KD_GEN_EOS_MAX");
+    GenEos eos;
+    for (int e = 0; e < KD_GEN_EOS_MAX; ++e) eos.id[e] = e < n_eos ? eos_ids_host[e] : 0;
+    eos.n = n_eos;
+    hipLaunchKernelGGL(k_gen_finish, dim3(1), dim3(64), 0, as_stream(stream), tok, cur_dev, nb, eos, fin, live);
+    KD_LAUNCH_CHECK("k_gen_finish");
     return KD_OK;
 }
 

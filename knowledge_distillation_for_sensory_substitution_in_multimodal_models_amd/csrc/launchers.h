@@ -86,6 +86,8 @@ int launch_gen_select_batch(const void* logits, int64_t ldl, int V, int64_t* seq
                             float penalty, int ngram, void* flags_ws, size_t ws_bytes, int64_t* out, void* stream);
 int launch_rope_rows(const float* cos_t, const float* sin_t, int hh, int rows, int nb, const int* cur_dev,
                      float* cos_rows, float* sin_rows, void* stream);
+int launch_gen_finish(const int64_t* tok, const int* cur_dev, int nb, const int64_t* eos_ids_host, int n_eos, int* fin,
+                      int* live, void* stream);
 size_t gemv_rows_ws(int rows, int N, int K, int epi);
 int launch_gemv_rows(const void* x, int64_t ldx, int rows, const void* W, int64_t ldw, const void* extra, void* y, int N,
                      int K, int epi, int I, const void* norm_w, float eps, void* ws, size_t ws_bytes, void* stream);

@@ -13,9 +13,12 @@ seed a per-layer KV cache [HKV, L + max_new_tokens, hd]; each new token then run
 every layer (kd_gemv with the RMSNorms fused in front and bias / residual / SwiGLU epilogues, kd_qkv_split with its
 RoPE row, split-KV kd_attn_decode) and kd_gen_select picks it on the device.  The position lives in a device counter, so
 every launch of a step has fixed arguments: the first step runs eagerly, the step is captured
-once as a HIP graph (torch.cuda.CUDAGraph) and replayed for the rest; steps past an EOS are
-discarded afterwards (one host read at the end instead of one per token).  Returns prompt + generated ids like
-transformers' generate (B = 1, as the evaluation runs it).
+once as a HIP graph (torch.cuda.CUDAGraph) and replayed for the rest.  kd_gen_finish, the last
+launch of the step, keeps on the device which rows have emitted an EOS; the loop reads that count
+every STOP_CHECK_EVERY steps (one 4-byte copy and an event wait between two replays) and ends once
+every row has, and the few steps past a row's EOS are discarded afterwards, so the result does
+not depend on how often it looks.  Returns prompt + generated ids like transformers' generate
+(B = 1, as the evaluation runs it).
 
 generate_batch() decodes up to 16 such prompts per step (ragged lengths, per-row device counters,
 batch-invariant kernels): the evaluation's one-question-at-a-time loop with the weights streamed
@@ -36,7 +39,7 @@ from __future__ import annotations
 import torch
 
 from . import ops
-from ._native import KD_GEMV_ROWS_MAX
+from ._native import KD_GEMV_ROWS_MAX, KD_GEN_EOS_MAX
 
 
 EOS_TOKEN_IDS = (151645,)   # <|im_end|>: generation_config.eos_token_id of the -ov-hf chat checkpoints
@@ -45,15 +48,92 @@ EOS_TOKEN_IDS = (151645,)   # <|im_end|>: generation_config.eos_token_id of the 
 FUSE_NORM_DEFAULT = True   # RMSNorm fused into the decode GEMVs (tools/bench_generate.py passes fuse_norm for A/B)
 
 
+# decode steps between two host reads of the rows still running (0: never stop early).  Measured
+# (profiles/generate_stop/bench.txt): a read costs < 0.1 ms, a step 1.2 - 1.6 ms, so every step wins
+STOP_CHECK_EVERY = 1
+
+
+def _stop_every(stop_check_every, who: str) -> int:
+    k = STOP_CHECK_EVERY if stop_check_every is None else int(stop_check_every)
+    if k < 0:
+        raise ValueError(f"{who}: stop_check_every must be >= 0")
+    return k
+
+
+def _stats_begin(stats):
+    if stats is not None:
+        for key in ("steps_run", "steps_max", "checks", "finished_at"):
+            stats[key] = []
+
+
+class _Stop:
+    """The early stop of one decode loop: kd_gen_finish keeps, on the device, every row's length at
+    its first EOS (fin) and the number of rows still running (live); the loop reads live every k
+    steps and ends once it is 0.  Inactive (k = 0, no EOS id, or more ids than kd_gen_finish takes)
+    it launches and reads nothing: the loop is then the plain max_new_tokens one."""
+
+    def __init__(self, model, nb: int, eos, k: int):
+        self.k, self.checks = k, 0
+        self.ids = sorted(eos)
+        self.active = k > 0 and 0 < len(self.ids) <= KD_GEN_EOS_MAX
+        if not self.active:
+            return
+        dev = model.device
+        self.fin = torch.zeros(nb, dtype=torch.int32, device=dev)
+        self.live = torch.zeros(1, dtype=torch.int32, device=dev)
+        cached = getattr(model, "_gen_stop_host", None)   # one pinned word and its event per model
+        if cached is None:
+            cached = (torch.zeros(1, dtype=torch.int32).pin_memory(), torch.cuda.Event())
+            model._gen_stop_host = cached
+        self.host, self.event = cached
+
+    def mark(self, tok, cur):
+        """Behind a select (also inside the captured step: its arguments never change)."""
+        if self.active:
+            ops.gen_finish(tok, cur, self.ids, self.fin, self.live)
+
+    def done(self, ran: int, n_steps: int) -> bool:
+        """After `ran` of n_steps steps, between two replays: has every row ended?  One 4-byte copy
+        and a wait on its own event (no device-wide synchronize: other streams keep running)."""
+        if not self.active or ran % self.k or ran >= n_steps:
+            return False
+        self.checks += 1
+        self.host.copy_(self.live, non_blocking=True)
+        self.event.record()
+        self.event.synchronize()
+        return int(self.host[0]) == 0
+
+    def ends(self):
+        """Per row the length at its first EOS (0: none), or None when inactive."""
+        return self.fin.tolist() if self.active else None
+
+
+def _stats_chunk(stats, ran, n_steps, checks, finished_at):
+    if stats is not None:
+        stats["steps_run"].append(ran)
+        stats["steps_max"].append(n_steps)
+        stats["checks"].append(checks)
+        stats["finished_at"].append(finished_at)
+
+
 @torch.no_grad()
 def generate(model, input_ids: torch.Tensor, pixel_values: torch.Tensor, image_sizes, max_new_tokens: int = 32,
              repetition_penalty: float = 1.0, no_repeat_ngram_size: int = 0, eos_token_id=EOS_TOKEN_IDS,
              pad_token_id: int | None = None, temperature: float | None = None, return_logits: bool = False,
-             graph: bool = True, fuse_norm: bool | None = None):
+             graph: bool = True, fuse_norm: bool | None = None, stop_check_every: int | None = None,
+             stats: dict | None = None):
     """-> int64 [1, L + n_new] on the device (and the bf16 logits row of every step if
     return_logits).  `temperature` is accepted for signature parity and ignored (greedy).
-    fuse_norm: RMSNorm fused into the q|k|v and gate|up GEMVs (default: FUSE_NORM_DEFAULT)."""
+    fuse_norm: RMSNorm fused into the q|k|v and gate|up GEMVs (default: FUSE_NORM_DEFAULT).
+    stop_check_every = k (default STOP_CHECK_EVERY; 0: never): with 1..KD_GEN_EOS_MAX EOS ids the
+    loop asks the device every k steps whether the row has emitted one and then ends, after
+    min(n, k * max(1, ceil(s / k))) of its n = max_new_tokens - 1 steps (s: the step that produced the
+    EOS, 0 for the prefill's token, n if none).  The result is the same bits for every k.
+    stats (a dict) receives one-entry lists steps_run, steps_max, checks (host reads) and finished_at
+    ([length at the first EOS, or 0])."""
     del temperature, pad_token_id   # greedy, batch of one: no padding of finished rows
+    k_stop = _stop_every(stop_check_every, "generate")
+    _stats_begin(stats)
     FUSE_NORM = FUSE_NORM_DEFAULT if fuse_norm is None else bool(fuse_norm)
     if input_ids.dim() != 2 or input_ids.shape[0] != 1:
         raise ValueError("generate: batch size 1 (as evaluate_onevision.py runs it)")
@@ -101,6 +181,8 @@ def generate(model, input_ids: torch.Tensor, pixel_values: torch.Tensor, image_s
     tok = seq[L:L + 1].clone()   # the token being decoded (kd_gen_select rewrites it each step)
     cos_row = torch.empty((1, cos.shape[1]), dtype=torch.float32, device=dev)
     sin_row = torch.empty_like(cos_row)
+    stop = _Stop(model, 1, eos, k_stop)
+    stop.mark(tok, cur)   # the prefill's token
 
     def step():
         ops.rope_row(cos, sin, cur, cos_row, sin_row)
@@ -125,10 +207,12 @@ def generate(model, input_ids: torch.Tensor, pixel_values: torch.Tensor, image_s
         hn, _, _ = ops.norm_fwd(x, P[lp + "norm.weight"], None, T.eps, rms=True, save_stats=False)
         lg = ops.gemv(hn, model.lm_head_weight())
         ops.gen_select(lg, seq, 0, repetition_penalty, no_repeat_ngram_size, out=tok, cur=cur)
+        stop.mark(tok, cur)
         return lg
 
     n_steps = smax - (L + 1)
     graph_obj = None
+    ran = 0
     for t_ in range(n_steps):
         if graph and t_ == 1:   # step 0 ran eagerly (warm-up: allocations, workspaces); capture the rest
             graph_obj = torch.cuda.CUDAGraph()
@@ -141,15 +225,23 @@ def generate(model, input_ids: torch.Tensor, pixel_values: torch.Tensor, image_s
             lg = step()
         if return_logits:
             steps.append(lg.clone())
-    n = smax
-    if eos:   # transformers stops after the first EOS; the steps past it are discarded
+        ran = t_ + 1
+        if stop.done(ran, n_steps):
+            break
+    end = 0   # the length at the first EOS (0: none); transformers stops there, the steps past it are discarded
+    fin = stop.ends()
+    if fin is not None:   # kept by the device (after an early stop the positions past it were never written)
+        end = fin[0]
+    elif eos:
         gen = seq[L:smax].tolist()
         for j, t_ in enumerate(gen):
             if t_ in eos:
-                n = L + j + 1
+                end = L + j + 1
                 break
-        if return_logits:
-            steps = steps[:n - L]
+    n = end or smax
+    if return_logits:
+        steps = steps[:n - L]
+    _stats_chunk(stats, ran, n_steps, stop.checks, [end])
     out = seq[:n].view(1, n)
     return (out, steps) if return_logits else out
 
@@ -160,7 +252,8 @@ MAX_BATCH = 16   # rows per decode step: the M dimension of the MFMA behind kd_g
 @torch.no_grad()
 def generate_batch(model, prompts, max_new_tokens: int = 32, repetition_penalty: float = 1.0,
                    no_repeat_ngram_size: int = 0, eos_token_id=EOS_TOKEN_IDS, pad_token_id: int | None = None,
-                   temperature: float | None = None, return_logits: bool = False, graph: bool = True):
+                   temperature: float | None = None, return_logits: bool = False, graph: bool = True,
+                   stop_check_every: int | None = None, stats: dict | None = None):
     """generate() for several prompts at once: prompts is a sequence of (input_ids [1, L_i],
     pixel_values [1, P_i, 3, 384, 384], image_sizes [1, 2]), ragged in L_i and P_i (no padding, no
     attention mask) -> list of int64 [1, L_i + n_i] (and, with return_logits, a list per row of the
@@ -171,9 +264,15 @@ def generate_batch(model, prompts, max_new_tokens: int = 32, repetition_penalty:
     decode steps then run up to MAX_BATCH rows through every layer at once, so a step streams the
     weights once for all rows (kd_gemv_batch / kd_attn_decode_batch / kd_gen_select_batch, per-row
     lengths in a device counter).  A row's tokens and logits do not depend on which other prompts
-    share its batch (bit-identical), longer lists run in chunks of MAX_BATCH.  All rows run
-    max_new_tokens steps; each is cut after its first EOS with one host read at the end."""
+    share its batch (bit-identical), longer lists run in chunks of MAX_BATCH.  Each row is cut
+    after its first EOS; a chunk stops decoding once all its rows have emitted one, which the loop
+    asks the device every stop_check_every = k steps (generate(): s is then the step that produced
+    the last row's first EOS), so the results are the same bits for every k.  stats (a dict)
+    receives, per chunk, steps_run, steps_max, checks and finished_at (per row the length at its
+    first EOS, or 0)."""
     del temperature, pad_token_id   # greedy; finished rows are cut, not padded
+    k_stop = _stop_every(stop_check_every, "generate_batch")
+    _stats_begin(stats)
     prompts = list(prompts)
     if not prompts:
         raise ValueError("generate_batch: no prompts")
@@ -185,14 +284,14 @@ def generate_batch(model, prompts, max_new_tokens: int = 32, repetition_penalty:
     outs, logs = [], []
     for c0 in range(0, len(prompts), MAX_BATCH):
         o, lg = _generate_rows(model, prompts[c0:c0 + MAX_BATCH], int(max_new_tokens), repetition_penalty,
-                               no_repeat_ngram_size, eos_token_id, return_logits, graph)
+                               no_repeat_ngram_size, eos_token_id, return_logits, graph, k_stop, stats)
         outs += o
         logs += lg
     return (outs, logs) if return_logits else outs
 
 
 def _generate_rows(model, prompts, max_new_tokens, repetition_penalty, no_repeat_ngram_size, eos_token_id,
-                   return_logits, graph):
+                   return_logits, graph, k_stop, stats):
     T = model.cfg.text
     dev = model.device
     nb = len(prompts)
@@ -222,7 +321,7 @@ def _generate_rows(model, prompts, max_new_tokens, repetition_penalty, no_repeat
         ops.gen_select(logits, seq[b], L, repetition_penalty, no_repeat_ngram_size)
 
     return _decode_rows(model, kc, vc, seq, Ls, steps, max_new_tokens, repetition_penalty, no_repeat_ngram_size, eos,
-                        return_logits, graph)
+                        return_logits, graph, k_stop, stats)
 
 
 def _decode_layers(model):
@@ -243,9 +342,10 @@ def _decode_layers(model):
 
 
 def _decode_rows(model, kc, vc, seq, Ls, steps, max_new_tokens, repetition_penalty, no_repeat_ngram_size, eos,
-                 return_logits, graph):
+                 return_logits, graph, k_stop, stats):
     """The batched decode loop behind generate_batch() and generate_grouped(): row b's caches hold
-    its L_b prompt positions, seq[b, L_b] its first new token and steps[b] that token's logits row."""
+    its L_b prompt positions, seq[b, L_b] its first new token and steps[b] that token's logits row.
+    The loop ends early once every row has emitted an EOS (_Stop)."""
     T, P = model.cfg.text, model.P
     dev = model.device
     nb, smax = seq.shape
@@ -260,6 +360,8 @@ def _decode_rows(model, kc, vc, seq, Ls, steps, max_new_tokens, repetition_penal
     tok = torch.stack([seq[b, Ls[b]] for b in range(nb)])   # the tokens being decoded
     cos_rows = torch.empty((nb, cos.shape[1]), dtype=torch.float32, device=dev)
     sin_rows = torch.empty_like(cos_rows)
+    stop = _Stop(model, nb, eos, k_stop)
+    stop.mark(tok, cur)   # the prefill's tokens
 
     def step():
         ops.rope_rows(cos, sin, cur, cos_rows, sin_rows)
@@ -274,10 +376,12 @@ def _decode_rows(model, kc, vc, seq, Ls, steps, max_new_tokens, repetition_penal
         hn, _, _ = ops.norm_fwd(x, P[lp + "norm.weight"], None, T.eps, rms=True, save_stats=False)
         lg = ops.gemv_batch(hn, model.lm_head_weight())
         ops.gen_select_batch(lg, seq, cur, repetition_penalty, no_repeat_ngram_size, out=tok)
+        stop.mark(tok, cur)
         return lg
 
     graph_obj = None
-    for t_ in range(max_new_tokens - 1):
+    n_steps, ran = max_new_tokens - 1, 0
+    for t_ in range(n_steps):
         if graph and t_ == 1:   # step 0 ran eagerly (warm-up: allocations, workspaces); capture the rest
             graph_obj = torch.cuda.CUDAGraph()
             with torch.cuda.graph(graph_obj):
@@ -291,15 +395,24 @@ def _decode_rows(model, kc, vc, seq, Ls, steps, max_new_tokens, repetition_penal
             lg = lg.clone()
             for b in range(nb):
                 steps[b].append(lg[b:b + 1])
-    ends = [L + max_new_tokens for L in Ls]
-    if eos:   # every row is cut after its own first EOS; the steps past it are discarded
-        host = seq.tolist()
-        for b, L in enumerate(Ls):
-            for j, t_ in enumerate(host[b][L:ends[b]]):
-                if t_ in eos:
-                    ends[b] = L + j + 1
-                    break
-            steps[b] = steps[b][:ends[b] - L]
+        ran = t_ + 1
+        if stop.done(ran, n_steps):
+            break
+    # every row is cut after its own first EOS (fin[b]: its length there, 0 if none); the steps past it are discarded
+    fin = stop.ends()
+    if fin is None:
+        fin = [0] * nb
+        if eos:
+            host = seq.tolist()
+            for b, L in enumerate(Ls):
+                for j, t_ in enumerate(host[b][L:L + max_new_tokens]):
+                    if t_ in eos:
+                        fin[b] = L + j + 1
+                        break
+    ends = [fin[b] or L + max_new_tokens for b, L in enumerate(Ls)]
+    for b, L in enumerate(Ls):
+        steps[b] = steps[b][:ends[b] - L]
+    _stats_chunk(stats, ran, n_steps, stop.checks, fin)
     outs = [seq[b, :ends[b]].view(1, ends[b]) for b in range(nb)]
     return outs, (steps if return_logits else [])
 
@@ -307,7 +420,8 @@ def _decode_rows(model, kc, vc, seq, Ls, steps, max_new_tokens, repetition_penal
 @torch.no_grad()
 def generate_grouped(model, groups, max_new_tokens: int = 32, repetition_penalty: float = 1.0,
                      no_repeat_ngram_size: int = 0, eos_token_id=EOS_TOKEN_IDS, pad_token_id: int | None = None,
-                     temperature: float | None = None, return_logits: bool = False, graph: bool = True):
+                     temperature: float | None = None, return_logits: bool = False, graph: bool = True,
+                     stop_check_every: int | None = None, stats: dict | None = None):
     """generate_batch() for questions grouped by image: groups is a sequence of (pixel_values
     [1, P, 3, 384, 384], image_sizes [1, 2], [input_ids [1, L_q], ...]) -> one list per group of int64
     [1, L_q + n_q] (and, with return_logits, the same nesting of per-step bf16 logits rows).
@@ -324,8 +438,13 @@ def generate_grouped(model, groups, max_new_tokens: int = 32, repetition_penalty
 
     Not bit-identical to generate_batch() on the same prompt (the prefix forward runs at M = P0
     instead of M = L and the suffix rows take the decode kernels); both are held to the same bounds
-    against the oracle."""
+    against the oracle.
+
+    stop_check_every and stats as in generate_batch(): a chunk of up to MAX_BATCH questions stops
+    decoding once all of them have emitted an EOS (one stats entry per chunk)."""
     del temperature, pad_token_id   # greedy; finished rows are cut, not padded
+    k_stop = _stop_every(stop_check_every, "generate_grouped")
+    _stats_begin(stats)
     groups = [(px, sizes, list(qs)) for px, sizes, qs in groups]
     if not groups:
         raise ValueError("generate_grouped: no groups")
@@ -358,7 +477,8 @@ def generate_grouped(model, groups, max_new_tokens: int = 32, repetition_penalty
     for c0 in range(0, len(items), MAX_BATCH):
         chunk = items[c0:c0 + MAX_BATCH]
         o, lg, carry = _generate_grouped_rows(model, chunk, carry, int(max_new_tokens), repetition_penalty,
-                                              no_repeat_ngram_size, eos_token_id, return_logits, graph)
+                                              no_repeat_ngram_size, eos_token_id, return_logits, graph, k_stop,
+                                              stats)
         for (gi, *_), ob, lb in zip(chunk, o, lg if return_logits else [None] * len(o)):
             outs[gi].append(ob)
             logs[gi].append(lb)
@@ -366,7 +486,7 @@ def generate_grouped(model, groups, max_new_tokens: int = 32, repetition_penalty
 
 
 def _generate_grouped_rows(model, chunk, carry, max_new_tokens, repetition_penalty, no_repeat_ngram_size, eos_token_id,
-                           return_logits, graph):
+                           return_logits, graph, k_stop, stats):
     T, P = model.cfg.text, model.P
     dev = model.device
     nb = len(chunk)
@@ -432,5 +552,5 @@ def _generate_grouped_rows(model, chunk, carry, max_new_tokens, repetition_penal
     ops.gen_select_batch(lg, seq, cur, repetition_penalty, no_repeat_ngram_size)   # seq[b, L_b]; cur = L_b + 1
     steps = [[lg[b:b + 1]] if return_logits else [] for b in range(nb)]
     outs, steps = _decode_rows(model, kc, vc, seq, Ls, steps, max_new_tokens, repetition_penalty,
-                               no_repeat_ngram_size, eos, return_logits, graph)
+                               no_repeat_ngram_size, eos, return_logits, graph, k_stop, stats)
     return outs, steps, carry

@@ -860,6 +860,25 @@ def gen_select_batch(logits: torch.Tensor, seq: torch.Tensor, cur: torch.Tensor,
             _stream())
 
 
+def gen_finish(tok: torch.Tensor, cur: torch.Tensor, eos_ids, fin: torch.Tensor, live: torch.Tensor) -> None:
+    """Latch the rows that just emitted an EOS token (kd_gen_finish): tok [nb] int64 (the tokens a
+    select just chose), cur [nb] int32 (the lengths after it), eos_ids 1..KD_GEN_EOS_MAX host ints;
+    fin[b] (int32, zeroed by the caller before the first call) becomes cur[b] at row b's first EOS
+    and is never changed again, live[0] (int32) the number of rows with fin[b] == 0."""
+    _require(tok, torch.int64, "gen_finish.tok")
+    _require(cur, torch.int32, "gen_finish.cur")
+    _require(fin, torch.int32, "gen_finish.fin")
+    _require(live, torch.int32, "gen_finish.live")
+    nb = tok.numel()
+    if cur.numel() != nb or fin.numel() != nb or live.numel() < 1 or not (
+            tok.is_contiguous() and cur.is_contiguous() and fin.is_contiguous()):
+        raise RuntimeError("gen_finish: tok, cur and fin must be contiguous [nb] tensors, live [1]")
+    ids = [int(e) for e in eos_ids]
+    host = (C.c_int64 * max(len(ids), 1))(*ids)
+    NV.call("kd_gen_finish", tok.data_ptr(), cur.data_ptr(), nb, C.addressof(host), len(ids), fin.data_ptr(),
+            live.data_ptr(), _stream())
+
+
 # ------------------------------------------------------------ grouped prefill ----
 def gemv_rows(x: torch.Tensor, w: torch.Tensor, *, bias=None, residual=None, swiglu_inter: int = 0, norm_w=None,
               eps: float = 1e-6, out: torch.Tensor | None = None) -> torch.Tensor:

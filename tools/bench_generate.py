@@ -6,27 +6,45 @@ prefill of one 336x336 prompt (L = 1536) + 32 greedy decode steps with the KV ca
                                                  measured in the same process
     python tools/bench_generate.py --grouped 6   also generate_grouped(): 16 prompts over ceil(16 / 6) images
                                                  (6 questions per image) against generate_batch() on the same
-                                                 16 prompts, same process; --grouped 1: nothing is shared"""
+                                                 16 prompts, same process; --grouped 1: nothing is shared
+    python tools/bench_generate.py --answer-tokens 3   (the default; 0: skip) the early stop on answers of K
+                                                 tokens: each row's K-th token of a run without EOS becomes an EOS
+                                                 id (at most 8 distinct ones), then 32 new tokens are timed with
+                                                 stop_check_every in {0, 1, 2, 4, 8} for generate() and, with
+                                                 --batch 16 / --grouped 6, for generate_batch() at --batch rows and
+                                                 generate_grouped(); --rows-from-set N: also for the first N rows
+                                                 whose own token is in the set (all of them end)
+    python tools/bench_generate.py --tree DIR    time the package of another checkout (the parent commit's, built) on
+                                                 the same prompts: where it has no stop_check_every, the answer legs
+                                                 time its plain calls with the same EOS ids (the baseline to
+                                                 interleave with)"""
 import argparse
+import inspect
 import sys
 import time
 from pathlib import Path
 
 import torch
 
-sys.path.insert(0, str(Path(__file__).resolve().parent.parent))
-from knowledge_distillation_for_sensory_substitution_in_multimodal_models_amd.data import synthetic_batch  # noqa
-from knowledge_distillation_for_sensory_substitution_in_multimodal_models_amd.generation import (  # noqa
-    generate, generate_batch, generate_grouped)
-from knowledge_distillation_for_sensory_substitution_in_multimodal_models_amd.modeling import (  # noqa
-    STUDENT_05B, LlavaOnevisionModel)
-
 ap = argparse.ArgumentParser()
 ap.add_argument("--batch", type=int, default=0, metavar="N",
                 help="also time generate_batch() at every nb in {1, 2, 4, 8, 16} up to N")
 ap.add_argument("--grouped", type=int, default=0, metavar="Q",
                 help="also time generate_grouped() on 16 prompts, Q questions per image, against generate_batch()")
+ap.add_argument("--answer-tokens", type=int, default=3, metavar="K",
+                help="time the early stop on answers of K tokens (0: skip)")
+ap.add_argument("--rows-from-set", type=int, default=0, metavar="N",
+                help="answer legs also on the first N rows whose own K-th token is in the EOS set")
+ap.add_argument("--tree", default=None, metavar="DIR", help="import the package from this checkout instead")
+ap.add_argument("--answer-only", action="store_true", help="skip the other legs' 32 / 96-token sweeps")
 args = ap.parse_args()
+
+sys.path.insert(0, str(Path(args.tree).resolve() if args.tree else Path(__file__).resolve().parent.parent))
+from knowledge_distillation_for_sensory_substitution_in_multimodal_models_amd.data import synthetic_batch  # noqa
+from knowledge_distillation_for_sensory_substitution_in_multimodal_models_amd.generation import (  # noqa
+    generate, generate_batch, generate_grouped)
+from knowledge_distillation_for_sensory_substitution_in_multimodal_models_amd.modeling import (  # noqa
+    STUDENT_05B, LlavaOnevisionModel)
 
 dev = torch.device("cuda:0")
 model = LlavaOnevisionModel(STUDENT_05B, dev, seed=2)
@@ -66,9 +84,10 @@ if args.batch > 0:
     # single-prompt run's); the marginal step cost from 32 -> 96 new tokens as above
     rows = [synthetic_batch(1, dev, L=1536, seed=s) for s in range(min(args.batch, 16))]
     prompts = [(r["depth_input_ids"], r["depth_pixel_values"], r["image_sizes"]) for r in rows]
+    prompts_b = prompts
     print(f"generate_batch, same process: single-prompt step {step1:.3f} ms/token")
     for nb in (1, 2, 4, 8, 16):
-        if nb > args.batch:
+        if nb > args.batch or args.answer_only:
             break
         tb = [best_of(lambda: generate_batch(model, prompts[:nb], max_new_tokens=n, **kw)) for n in (32, 96)]
         step = (tb[1] - tb[0]) / 64 * 1e3
@@ -96,8 +115,78 @@ if args.grouped > 0:
         prompts += [(q, r["depth_pixel_values"], r["image_sizes"]) for q in qs]
     print(f"generate_grouped, Q = {Q}: {NP} prompts over {len(groups)} images (L = 1536, {1536 - P0} tokens after "
           f"the image), against generate_batch on the same prompts, same process")
-    for n in (32, 96):
+    for n in () if args.answer_only else (32, 96):
         tg = best_of(lambda: generate_grouped(model, groups, max_new_tokens=n, **kw))
         tb = best_of(lambda: generate_batch(model, prompts, max_new_tokens=n, **kw))
         print(f"  {n:2d} new tokens: generate_grouped {tg * 1e3:7.1f} ms per call, generate_batch {tb * 1e3:7.1f} ms "
               f"per call, ratio {tg / tb:.3f} ({tb / tg:.2f}x)")
+
+
+# ---------------------------------------------------------------- the early stop on short answers ----
+HAS_STOP = "stop_check_every" in inspect.signature(generate).parameters
+KW2 = dict(repetition_penalty=1.2, no_repeat_ngram_size=2)
+L0 = 1536
+
+
+def answer_leg(name, rows, call):
+    """rows: what call(rows, n_new, **kw) -> [int64 [1, L0 + n], ...] (one per row) takes."""
+    K = args.answer_tokens
+    full = [o[0, L0:].tolist() for o in call(rows, 32, eos_token_id=())]
+    ids, owners = [], []
+    for r, new in enumerate(full):   # each row's K-th token, until 8 distinct ids are taken
+        if new[K - 1] in ids or len(ids) < 8:
+            owners.append(r)
+            if new[K - 1] not in ids:
+                ids.append(new[K - 1])
+    eos = tuple(ids)
+
+    def lengths(sel):
+        return [next((j + 1 for j, t in enumerate(full[r]) if t in eos), 32) for r in sel]
+
+    legs = [("", list(range(len(rows))))]
+    if 0 < args.rows_from_set < len(rows):
+        legs.append((f", first {min(args.rows_from_set, len(owners))} rows of the set", owners[:args.rows_from_set]))
+    for tag, sel in legs:
+        sub = [rows[r] for r in sel]
+        ln = lengths(sel)
+        print(f"{name}{tag}: answers of {K} tokens, EOS = the K-th token of {len(owners)} of {len(rows)} rows "
+              f"({len(eos)} ids); realised lengths {ln}")
+        t_no = [best_of(lambda: call(sub, n, eos_token_id=())) for n in (32, 96)]
+        step = (t_no[1] - t_no[0]) / 64 * 1e3
+        print(f"  no EOS id (the stop is inactive): {t_no[0] * 1e3:7.2f} ms per call of 32 tokens, marginal step "
+              f"{step:.3f} ms (32 -> 96)")
+        rep = [best_of(lambda: call(sub, 32, eos_token_id=())) * 1e3 for _ in range(5)]
+        print("  no EOS id, best of 3, five times: " + " ".join(f"{t:.2f}" for t in rep) +
+              f" ms (spread {(max(rep) / min(rep) - 1) * 100:.2f} %)")
+        if not HAS_STOP:
+            t = best_of(lambda: call(sub, 32, eos_token_id=eos)) * 1e3
+            print(f"  this tree has no stop_check_every: {t:7.2f} ms per call of 32 tokens with the EOS ids, 31 steps")
+            continue
+        t0_ = None
+        for k in (0, 1, 2, 4, 8):
+            st = {}
+            t = best_of(lambda: call(sub, 32, eos_token_id=eos, stop_check_every=k, stats=st)) * 1e3
+            t0_ = t if k == 0 else t0_
+            skipped = sum(st["steps_max"]) - sum(st["steps_run"])
+            frac = f", {(t0_ - t) / (skipped * step):.2f} x (skipped steps x marginal step)" if skipped else ""
+            print(f"  stop_check_every={k}: {t:7.2f} ms per call; steps_run {st['steps_run']} of {st['steps_max']}, "
+                  f"checks {st['checks']}; {t0_ - t:6.2f} ms less than k=0{frac}")
+
+
+if args.answer_tokens > 0:
+    one = (b["depth_input_ids"], b["depth_pixel_values"], b["image_sizes"])
+    answer_leg("generate", [one],
+               lambda rows, n, **k: [generate(model, *rows[0], max_new_tokens=n, **KW2, **k)])
+    if args.batch > 0:
+        answer_leg(f"generate_batch nb={len(prompts_b)}", prompts_b,
+                   lambda rows, n, **k: generate_batch(model, rows, max_new_tokens=n, **KW2, **k))
+    if args.grouped > 0:
+        def call_grouped(rows, n, **k):
+            gs = {}
+            for gi, q in rows:   # the questions kept, under their images
+                gs.setdefault(gi, []).append(q)
+            outs = generate_grouped(model, [(groups[gi][0], groups[gi][1], qs) for gi, qs in gs.items()],
+                                    max_new_tokens=n, **KW2, **k)
+            return [o for g in outs for o in g]
+        answer_leg(f"generate_grouped Q={args.grouped}", [(gi, q) for gi, g in enumerate(groups) for q in g[2]],
+                   call_grouped)
