@@ -17,9 +17,25 @@
 // k_gen_select_batch, k_rope_rows; and for generate_grouped() (one image prefill shared by its
 // questions) the suffix rows of a chunk: k_gemv_slabs (k_gemv_batch for more than 16 rows, row for
 // row the same bits) and k_attn_extend_part (ragged suffix queries against prefix + own suffix).
+//
+// Each algorithm has one body.  The single-row and the batched form of a kernel differ in where a
+// row's pointers and length come from, not in what is computed, so they share a __forceinline__
+// device function and keep only their own setup and stores:
+//   gen_select_row   flags, processors, argmax: k_gen_select, k_gen_select_batch
+//   gb_row_rstd, gb_stage_slab, gb_wave_order_sum, gb_store
+//                    the 16-row slab of k_gemv_batch and k_gemv_slabs, which is why a row of
+//                    kd_gemv_rows has kd_gemv_batch's bits; k_gemv_batch_reduce serves both
+//   k_rope_rows      also kd_rope_row (one row)
+// and the launchers share dispatch_epi / dispatch_hd (runtime value -> template instance) and
+// check_gemv_args / check_attn_args.  The one pair left as two copies is the dot-product loop of
+// k_gemv and k_gemv_wide (a workgroup per output; k_gemv_rows before kd_gemv_rows took that name
+// for something else): shared, it was measurably slower (see there).
 #include "common.h"
 
 #include <algorithm>
+#include <climits>
+#include <string>
+#include <type_traits>
 
 namespace kd {
 
@@ -164,6 +180,12 @@ __device__ __forceinline__ void stage_x(const bf16* __restrict__ x, const bf16* 
 // (two weight rows, n and I + n, for the SwiGLU form).  Weight rows are read once, 16 B per lane,
 // so the decode step streams its weights at HBM rate instead of running 256-row GEMM tiles at
 // M = 1.  EPI: 0 none, 1 + bias[n], 2 + residual[n], 3 silu(row n) * (row I + n).
+//
+// k_gemv and k_gemv_wide keep their own copy of the dot-product loop and the epilogue on purpose.
+// With the two behind one __forceinline__ body (k stride and reduction as parameters) hipcc
+// schedules the loop differently (same registers, same occupancy, same bits), and these 5 - 9 us
+// kernels, ~100 launches per token, came out 3 - 7 % slower in a kernel trace: generate() lost
+// 0.8 ms of 48 (profiles/decode_dedupe/bench_ab.txt).  A change to one loop belongs in the other.
 template <int EPI>
 __global__ void __launch_bounds__(NT) k_gemv(const bf16* __restrict__ x, const bf16* __restrict__ W, int64_t ldw,
                                              const bf16* __restrict__ extra, bf16* __restrict__ y, int N, int K,
@@ -196,11 +218,12 @@ __global__ void __launch_bounds__(NT) k_gemv(const bf16* __restrict__ x, const b
     }
 }
 
-// Row-per-workgroup form of k_gemv for few output rows with long K (o_proj / down_proj of the
+// Workgroup-per-output form of k_gemv for few output rows with long K (o_proj / down_proj of the
 // 0.5B student: N = 896, K up to 4864): 256 threads split K, block reduction, so N workgroups
-// instead of N / 4 keep every CU streaming.
+// instead of N / 4 keep every CU streaming.  (k_gemv_rows until the public kd_gemv_rows, which is
+// k_gemv_slabs below, took that name for something else.)
 template <int EPI>
-__global__ void __launch_bounds__(NT) k_gemv_rows(const bf16* __restrict__ x, const bf16* __restrict__ W, int64_t ldw,
+__global__ void __launch_bounds__(NT) k_gemv_wide(const bf16* __restrict__ x, const bf16* __restrict__ W, int64_t ldw,
                                                   const bf16* __restrict__ extra, bf16* __restrict__ y, int K, int I,
                                                   const bf16* __restrict__ norm_w, float eps) {
     extern __shared__ float xs[];
@@ -230,16 +253,16 @@ __global__ void __launch_bounds__(NT) k_gemv_rows(const bf16* __restrict__ x, co
     }
 }
 
-// One workgroup of 1024 threads: flags in the workspace (bit 0 = seen, bit 1 = banned), then
-// the processed-score argmax.  seq [len + 1] int64 (the new token is written at seq[len]).
-__global__ void __launch_bounds__(1024) k_gen_select(const bf16* __restrict__ logits, int V, int64_t* __restrict__ seq,
-                                                     int len, int* __restrict__ cur_dev, float penalty, int ngram,
-                                                     uint8_t* __restrict__ flags, int64_t* __restrict__ out) {
+// The token choice of one row by one workgroup of 1024 threads: V bytes of flags (bit 0 = seen,
+// bit 1 = banned) from the len ids of seq, then the processed-score argmax, which thread 0 returns
+// (the other threads' value is not the row's).  The vector paths need 16-byte aligned logits and
+// flags (the single-row workspace always is; row b of a batch may not be) and fall back to bytes.
+__device__ __forceinline__ int gen_select_row(const bf16* __restrict__ logits, int V, const int64_t* __restrict__ seq,
+                                              int len, float penalty, int ngram, uint8_t* __restrict__ flags) {
     __shared__ float sv[16];
     __shared__ int si[16];
-    if (cur_dev) len = *cur_dev;
-    {   // clear the flags, 16 B per store (flags is 256-B aligned workspace)
-        const int v16 = V >> 4;
+    {   // clear the flags, 16 B per store
+        const int v16 = ((uintptr_t)flags & 15) == 0 ? V >> 4 : 0;
         for (int i = threadIdx.x; i < v16; i += blockDim.x) ((u32x4*)flags)[i] = u32x4{0u, 0u, 0u, 0u};
         for (int i = (v16 << 4) + threadIdx.x; i < V; i += blockDim.x) flags[i] = 0;
     }
@@ -270,7 +293,8 @@ __global__ void __launch_bounds__(1024) k_gen_select(const bf16* __restrict__ lo
         if (f & 2) s = -INFINITY;
         if (s > best || (s == best && i < bi)) { best = s; bi = i; }   // NaN never wins
     };
-    const int v8 = ((uintptr_t)logits & 15) == 0 ? V >> 3 : 0;   // 8 logits (16 B) + 8 flags per step
+    // 8 logits (16 B) + 8 flags per step
+    const int v8 = (((uintptr_t)logits & 15) == 0 && ((uintptr_t)flags & 7) == 0) ? V >> 3 : 0;
     for (int c = threadIdx.x; c < v8; c += blockDim.x) {
         const bf16x8 lv = ((const bf16x8*)logits)[c];
         const u32x2 fv = ((const u32x2*)flags)[c];
@@ -291,19 +315,21 @@ __global__ void __launch_bounds__(1024) k_gen_select(const bf16* __restrict__ lo
         for (int k = 1; k < (int)(blockDim.x >> 6); ++k)
             if (sv[k] > best || (sv[k] == best && si[k] < bi)) { best = sv[k]; bi = si[k]; }
         if (bi == 0x7fffffff) bi = 0;   // every score -inf: torch.argmax returns 0
+    }
+    return bi;
+}
+
+// seq [len + 1] int64 (the new token is written at seq[len]); len = *cur_dev, then incremented,
+// when cur_dev is given.
+__global__ void __launch_bounds__(1024) k_gen_select(const bf16* __restrict__ logits, int V, int64_t* __restrict__ seq,
+                                                     int len, int* __restrict__ cur_dev, float penalty, int ngram,
+                                                     uint8_t* __restrict__ flags, int64_t* __restrict__ out) {
+    if (cur_dev) len = *cur_dev;
+    const int bi = gen_select_row(logits, V, seq, len, penalty, ngram, flags);
+    if (threadIdx.x == 0) {
         seq[len] = bi;
         if (out) *out = bi;
         if (cur_dev) *cur_dev = len + 1;
-    }
-}
-
-// cos/sin row of position *cur_dev - 1 into fixed one-row buffers (what kd_qkv_split reads).
-__global__ void k_rope_row(const float* __restrict__ cos_t, const float* __restrict__ sin_t, int hh,
-                           const int* __restrict__ cur_dev, float* __restrict__ cos_row, float* __restrict__ sin_row) {
-    const int pos = *cur_dev - 1;
-    for (int i = threadIdx.x; i < hh; i += blockDim.x) {
-        cos_row[i] = cos_t[(size_t)pos * hh + i];
-        sin_row[i] = sin_t[(size_t)pos * hh + i];
     }
 }
 
@@ -450,6 +476,96 @@ constexpr int GB_MAX_STEPS = 48;    // 32-k steps per K slice: 16 x (1536 + 8) b
 constexpr int GB_PAD = 8;           // bf16 per LDS row: rows 16 B apart in the banks
 constexpr int GB_PF = 8;            // weight fragments per wave loaded ahead of the x staging
 
+// ---- the 16-row slab of x, shared by k_gemv_batch and k_gemv_slabs (kd_gemv_rows): a row's bits
+// are the same in both because this code is the same ----
+
+// 1/rms of each of the slab's nb rows, over the whole row, into rstd_s: 16 lanes per row, the same
+// order in every slot.  Ends on a barrier.
+__device__ __forceinline__ void gb_row_rstd(const bf16* __restrict__ x, int64_t ldx, int nb, int K, float eps,
+                                            float* rstd_s) {
+    const int b = threadIdx.x >> 4, sub = threadIdx.x & 15;
+    float ss = 0.f;
+    if (b < nb) {
+        const bf16* xr = x + (size_t)b * ldx;
+#pragma unroll 8
+        for (int k = sub * 8; k < K; k += 128) {
+            const bf16x8 v = *(const bf16x8*)(xr + k);
+#pragma unroll
+            for (int e = 0; e < 8; ++e) ss += (float)v[e] * (float)v[e];
+        }
+    }
+#pragma unroll
+    for (int o = 8; o > 0; o >>= 1) ss += __shfl_xor(ss, o, 64);
+    if (sub == 0) rstd_s[b] = rsqrtf(ss / K + eps);
+    __syncthreads();
+}
+
+// Columns [kb, kb + slice_steps * 32) of the slab into xs ([16][slice_steps * 32 + GB_PAD] bf16), with
+// norm_w as the RMSNorm output rounded to bf16; rows >= nb and the K tail are zeros.  Ends on a barrier.
+__device__ __forceinline__ void gb_stage_slab(const bf16* __restrict__ x, int64_t ldx, int nb, int K, int kb,
+                                              int slice_steps, const bf16* __restrict__ norm_w, float eps,
+                                              float* rstd_s, bf16* xs) {
+    if (norm_w) gb_row_rstd(x, ldx, nb, K, eps, rstd_s);
+    const int cpr = slice_steps * 4, XLD = slice_steps * 32 + GB_PAD;   // 16-B chunks per staged row
+    const bf16x8 zero8 = {};
+#pragma unroll 4
+    for (int idx = threadIdx.x; idx < GB_ROWS * cpr; idx += NT) {
+        const int b = idx / cpr, c = idx - b * cpr, k = kb + c * 8;
+        const bool in = b < nb && k < K;
+        const int bc = min(b, nb - 1), kc8 = min(k, K - 8);   // the loads stay unconditional, inside x
+        bf16x8 v = *(const bf16x8*)(x + (size_t)bc * ldx + kc8);
+        if (norm_w) {
+            const bf16x8 nw = *(const bf16x8*)(norm_w + kc8);
+            const float rstd = rstd_s[bc];
+#pragma unroll
+            for (int e = 0; e < 8; ++e) v[e] = (bf16)((float)v[e] * rstd * (float)nw[e]);
+        }
+        *(bf16x8*)(xs + b * XLD + c * 8) = in ? v : zero8;
+    }
+    __syncthreads();
+}
+
+// The 4 waves' K shares of a tile, summed in wave order through red_s: true on wave 0, which then
+// holds the sums.  The barrier inside also ends every wave's reads of xs and rstd_s.
+template <int NACC>
+__device__ __forceinline__ bool gb_wave_order_sum(f32x4 (&red_s)[NACC][NT / 64][64], int w, int lane, f32x4& acc0,
+                                                  f32x4& acc1) {
+    red_s[0][w][lane] = acc0;
+    if constexpr (NACC == 2) red_s[1][w][lane] = acc1;
+    __syncthreads();
+    if (w != 0) return false;
+    acc0 = ((red_s[0][0][lane] + red_s[0][1][lane]) + red_s[0][2][lane]) + red_s[0][3][lane];
+    if constexpr (NACC == 2) acc1 = ((red_s[1][0][lane] + red_s[1][1][lane]) + red_s[1][2][lane]) + red_s[1][3][lane];
+    return true;
+}
+
+// One D fragment (column n = lane & 15, slab row (lane >> 4) * 4 + r, global row row0 + that):
+// through the epilogue into y when K is not split, else as slice ks of the partials
+// [ksplit, NACC, rows16, N].
+template <int EPI>
+__device__ __forceinline__ void gb_store(const f32x4& acc0, const f32x4& acc1, int lane, int nb, size_t row0,
+                                         int rows16, int n, int N, int ks, int ksplit,
+                                         const bf16* __restrict__ extra, bf16* __restrict__ y,
+                                         float* __restrict__ part) {
+    constexpr int NACC = EPI == 3 ? 2 : 1;
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+        const int b = (lane >> 4) * 4 + r;
+        if (b >= nb) continue;
+        const size_t gr = row0 + b;
+        if (ksplit == 1) {
+            float v = acc0[r];
+            if constexpr (EPI == 1) v += (float)extra[n];
+            if constexpr (EPI == 2) v += (float)extra[gr * N + n];
+            if constexpr (EPI == 3) v = silu_fast(acc0[r]) * acc1[r];
+            y[gr * N + n] = (bf16)v;
+        } else {
+            part[(((size_t)ks * NACC) * rows16 + gr) * N + n] = acc0[r];
+            if constexpr (EPI == 3) part[(((size_t)ks * NACC + 1) * rows16 + gr) * N + n] = acc1[r];
+        }
+    }
+}
+
 template <int EPI>
 __global__ void __launch_bounds__(NT) k_gemv_batch(const bf16* __restrict__ x, int64_t ldx, const bf16* __restrict__ W,
                                                    int64_t ldw, const bf16* __restrict__ extra, bf16* __restrict__ y,
@@ -483,39 +599,7 @@ __global__ void __launch_bounds__(NT) k_gemv_batch(const bf16* __restrict__ x, i
         pf0[i] = *(const bf16x8*)(r0 + (in ? k : 0));
         if constexpr (EPI == 3) pf1[i] = *(const bf16x8*)(r1 + (in ? k : 0));
     }
-    if (norm_w) {   // per-row 1/rms over the whole row: 16 lanes per row, the same order in every slot
-        const int b = threadIdx.x >> 4, sub = threadIdx.x & 15;
-        float ss = 0.f;
-        if (b < nb) {
-            const bf16* xr = x + (size_t)b * ldx;
-#pragma unroll 8
-            for (int k = sub * 8; k < K; k += 128) {
-                const bf16x8 v = *(const bf16x8*)(xr + k);
-#pragma unroll
-                for (int e = 0; e < 8; ++e) ss += (float)v[e] * (float)v[e];
-            }
-        }
-#pragma unroll
-        for (int o = 8; o > 0; o >>= 1) ss += __shfl_xor(ss, o, 64);
-        if (sub == 0) rstd_s[b] = rsqrtf(ss / K + eps);
-        __syncthreads();
-    }
-    const int cpr = slice_steps * 4;   // 16-B chunks per staged row
-#pragma unroll 4
-    for (int idx = threadIdx.x; idx < GB_ROWS * cpr; idx += NT) {
-        const int b = idx / cpr, c = idx - b * cpr, k = kb + c * 8;
-        const bool in = b < nb && k < K;   // else zeros: rows >= nb and the K tail
-        const int bc = min(b, nb - 1), kc8 = min(k, K - 8);   // the loads stay unconditional, inside x
-        bf16x8 v = *(const bf16x8*)(x + (size_t)bc * ldx + kc8);
-        if (norm_w) {
-            const bf16x8 nw = *(const bf16x8*)(norm_w + kc8);
-            const float rstd = rstd_s[bc];
-#pragma unroll
-            for (int e = 0; e < 8; ++e) v[e] = (bf16)((float)v[e] * rstd * (float)nw[e]);
-        }
-        *(bf16x8*)(xs + b * XLD + c * 8) = in ? v : zero8;
-    }
-    __syncthreads();
+    gb_stage_slab(x, ldx, nb, K, kb, slice_steps, norm_w, eps, rstd_s, xs);
     const bf16* xr = xs + col * XLD + kq - kb;
     f32x4 acc0 = {0.f, 0.f, 0.f, 0.f}, acc1 = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
@@ -540,44 +624,25 @@ __global__ void __launch_bounds__(NT) k_gemv_batch(const bf16* __restrict__ x, i
             acc1 = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, in ? l1 : zero8, acc1, 0, 0, 0);
         }
     }
-    if (!wave_n) {   // the 4 waves' K shares, summed in wave order
-        red_s[0][w][lane] = acc0;
-        if constexpr (EPI == 3) red_s[1][w][lane] = acc1;
-        __syncthreads();
-        if (w != 0) return;
-        acc0 = ((red_s[0][0][lane] + red_s[0][1][lane]) + red_s[0][2][lane]) + red_s[0][3][lane];
-        if constexpr (EPI == 3) acc1 = ((red_s[1][0][lane] + red_s[1][1][lane]) + red_s[1][2][lane]) + red_s[1][3][lane];
-    }
+    if (!wave_n && !gb_wave_order_sum(red_s, w, lane, acc0, acc1)) return;
     if (n >= N) return;
-#pragma unroll
-    for (int r = 0; r < 4; ++r) {   // D: column n = lane & 15, batch row (lane >> 4) * 4 + r
-        const int b = (lane >> 4) * 4 + r;
-        if (b >= nb) continue;
-        if (ksplit == 1) {
-            float v = acc0[r];
-            if constexpr (EPI == 1) v += (float)extra[n];
-            if constexpr (EPI == 2) v += (float)extra[(size_t)b * N + n];
-            if constexpr (EPI == 3) v = silu_fast(acc0[r]) * acc1[r];
-            y[(size_t)b * N + n] = (bf16)v;
-        } else {
-            part[(((size_t)ks * NACC) * GB_ROWS + b) * N + n] = acc0[r];
-            if constexpr (EPI == 3) part[(((size_t)ks * NACC + 1) * GB_ROWS + b) * N + n] = acc1[r];
-        }
-    }
+    gb_store<EPI>(acc0, acc1, lane, nb, 0, GB_ROWS, n, N, ks, ksplit, extra, y, part);
 }
 
-// Sum of the K slices of k_gemv_batch in slice order, then the epilogue.  Grid (ceil(N / 256), 16):
-// fixed by N, rows >= nb exit.
+// Sum of the K slices in slice order, then the epilogue, over `rows` rows of partials
+// [ksplit, NACC, rows16, N] (k_gemv_batch: rows16 = 16).  Grid (ceil(N / 256), >= rows): rows past
+// `rows` exit.
 template <int EPI>
 __global__ void __launch_bounds__(NT) k_gemv_batch_reduce(const float* __restrict__ part, const bf16* __restrict__ extra,
-                                                          bf16* __restrict__ y, int nb, int N, int ksplit) {
+                                                          bf16* __restrict__ y, int rows, int rows16, int N,
+                                                          int ksplit) {
     constexpr int NACC = EPI == 3 ? 2 : 1;
     const int b = blockIdx.y, n = blockIdx.x * NT + threadIdx.x;
-    if (b >= nb || n >= N) return;
+    if (b >= rows || n >= N) return;
     float a0 = 0.f, a1 = 0.f;
     for (int ks = 0; ks < ksplit; ++ks) {
-        a0 += part[(((size_t)ks * NACC) * GB_ROWS + b) * N + n];
-        if constexpr (EPI == 3) a1 += part[(((size_t)ks * NACC + 1) * GB_ROWS + b) * N + n];
+        a0 += part[(((size_t)ks * NACC) * rows16 + b) * N + n];
+        if constexpr (EPI == 3) a1 += part[(((size_t)ks * NACC + 1) * rows16 + b) * N + n];
     }
     float v = a0;
     if constexpr (EPI == 1) v += (float)extra[n];
@@ -587,68 +652,16 @@ __global__ void __launch_bounds__(NT) k_gemv_batch_reduce(const float* __restric
 }
 
 // k_gen_select for row b = blockIdx.x: its own logits row, sequence (row stride smax), length
-// cur_dev[b] and V bytes of flags; the arithmetic is k_gen_select's.
+// cur_dev[b] and V bytes of flags.  A full row (len == smax) still reports its token in out[b].
 __global__ void __launch_bounds__(1024) k_gen_select_batch(const bf16* __restrict__ logits_all, int64_t ldl, int V,
                                                            int64_t* __restrict__ seq_all, int smax,
                                                            int* __restrict__ cur_dev, float penalty, int ngram,
                                                            uint8_t* __restrict__ flags_all, int64_t* __restrict__ out) {
-    __shared__ float sv[16];
-    __shared__ int si[16];
     const int b = blockIdx.x;
-    const bf16* logits = logits_all + (size_t)b * ldl;
     int64_t* seq = seq_all + (size_t)b * smax;
-    uint8_t* flags = flags_all + (size_t)b * V;
     const int len = max(0, min(cur_dev[b], smax));   // the ids read never leave the row
-    {
-        const int v16 = ((uintptr_t)flags & 15) == 0 ? V >> 4 : 0;
-        for (int i = threadIdx.x; i < v16; i += blockDim.x) ((u32x4*)flags)[i] = u32x4{0u, 0u, 0u, 0u};
-        for (int i = (v16 << 4) + threadIdx.x; i < V; i += blockDim.x) flags[i] = 0;
-    }
-    __syncthreads();
-    if (penalty != 1.0f)
-        for (int i = threadIdx.x; i < len; i += blockDim.x) {
-            const int64_t t = seq[i];
-            if (t >= 0 && t < V) flags[t] |= 1;
-        }
-    __syncthreads();   // the two processors OR different bits into the same bytes
-    if (ngram > 0 && len + 1 >= ngram)
-        for (int i = threadIdx.x; i + ngram <= len; i += blockDim.x) {
-            bool match = true;
-            for (int k = 0; k < ngram - 1; ++k) match &= seq[i + k] == seq[len - ngram + 1 + k];
-            if (match) {
-                const int64_t t = seq[i + ngram - 1];
-                if (t >= 0 && t < V) flags[t] |= 2;
-            }
-        }
-    __syncthreads();
-    float best = -INFINITY;
-    int bi = 0x7fffffff;
-    auto consider = [&](int i, float s, uint32_t f) {
-        if (f & 1) s = s < 0.f ? __fmul_rn(s, penalty) : __fdiv_rn(s, penalty);
-        if (f & 2) s = -INFINITY;
-        if (s > best || (s == best && i < bi)) { best = s; bi = i; }   // NaN never wins
-    };
-    const int v8 = (((uintptr_t)logits & 15) == 0 && ((uintptr_t)flags & 7) == 0) ? V >> 3 : 0;
-    for (int c = threadIdx.x; c < v8; c += blockDim.x) {
-        const bf16x8 lv = ((const bf16x8*)logits)[c];
-        const u32x2 fv = ((const u32x2*)flags)[c];
-#pragma unroll
-        for (int e = 0; e < 8; ++e) consider(c * 8 + e, (float)lv[e], ((e < 4 ? fv.x : fv.y) >> (8 * (e & 3))) & 255u);
-    }
-    for (int i = (v8 << 3) + threadIdx.x; i < V; i += blockDim.x) consider(i, (float)logits[i], flags[i]);
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) {
-        const float ov = __shfl_xor(best, off, 64);
-        const int oi = __shfl_xor(bi, off, 64);
-        if (ov > best || (ov == best && oi < bi)) { best = ov; bi = oi; }
-    }
-    const int w = threadIdx.x >> 6;
-    if ((threadIdx.x & 63) == 0) { sv[w] = best; si[w] = bi; }
-    __syncthreads();
+    const int bi = gen_select_row(logits_all + (size_t)b * ldl, V, seq, len, penalty, ngram, flags_all + (size_t)b * V);
     if (threadIdx.x == 0) {
-        for (int k = 1; k < (int)(blockDim.x >> 6); ++k)
-            if (sv[k] > best || (sv[k] == best && si[k] < bi)) { best = sv[k]; bi = si[k]; }
-        if (bi == 0x7fffffff) bi = 0;   // every score -inf: torch.argmax returns 0
         if (len < smax) seq[len] = bi;
         if (out) out[b] = bi;
         cur_dev[b] = len + 1;
@@ -743,45 +756,12 @@ __global__ void __launch_bounds__(NT) k_gemv_slabs(const bf16* __restrict__ x, i
         }
     }
     const int rows16 = (rows + GB_ROWS - 1) / GB_ROWS * GB_ROWS;
-    const int cpr = slice_steps * 4;   // 16-B chunks per staged row
     const bf16* xr = xs + col * XLD + kq - kb;
     // slabs blockIdx.z, blockIdx.z + gridDim.z, ...: a slab is a chain of dependent round trips (norm,
     // staging, MFMA, LDS sum), so up to GS_SLAB_GROUPS workgroups per tile share a CU and overlap them
     for (int row0 = blockIdx.z * GB_ROWS; row0 < rows; row0 += gridDim.z * GB_ROWS) {
-        const bf16* xsl = x + (size_t)row0 * ldx;
         const int nb = min(GB_ROWS, rows - row0);
-        if (norm_w) {   // per-row 1/rms over the whole row: 16 lanes per row, the same order in every slot
-            const int b = threadIdx.x >> 4, sub = threadIdx.x & 15;
-            float ss = 0.f;
-            if (b < nb) {
-                const bf16* xrow = xsl + (size_t)b * ldx;
-#pragma unroll 8
-                for (int k = sub * 8; k < K; k += 128) {
-                    const bf16x8 v = *(const bf16x8*)(xrow + k);
-#pragma unroll
-                    for (int e = 0; e < 8; ++e) ss += (float)v[e] * (float)v[e];
-                }
-            }
-#pragma unroll
-            for (int o = 8; o > 0; o >>= 1) ss += __shfl_xor(ss, o, 64);
-            if (sub == 0) rstd_s[b] = rsqrtf(ss / K + eps);
-            __syncthreads();
-        }
-#pragma unroll 4
-        for (int idx = threadIdx.x; idx < GB_ROWS * cpr; idx += NT) {
-            const int b = idx / cpr, c = idx - b * cpr, k = kb + c * 8;
-            const bool in = b < nb && k < K;   // else zeros: rows >= nb and the K tail
-            const int bc = min(b, nb - 1), kc8 = min(k, K - 8);   // the loads stay unconditional, inside x
-            bf16x8 v = *(const bf16x8*)(xsl + (size_t)bc * ldx + kc8);
-            if (norm_w) {
-                const bf16x8 nw = *(const bf16x8*)(norm_w + kc8);
-                const float rstd = rstd_s[bc];
-#pragma unroll
-                for (int e = 0; e < 8; ++e) v[e] = (bf16)((float)v[e] * rstd * (float)nw[e]);
-            }
-            *(bf16x8*)(xs + b * XLD + c * 8) = in ? v : zero8;
-        }
-        __syncthreads();
+        gb_stage_slab(x + (size_t)row0 * ldx, ldx, nb, K, kb, slice_steps, norm_w, eps, rstd_s, xs);
         f32x4 acc0 = {0.f, 0.f, 0.f, 0.f}, acc1 = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
         for (int i = 0; i < GS_FR; ++i) {
@@ -792,49 +772,11 @@ __global__ void __launch_bounds__(NT) k_gemv_slabs(const bf16* __restrict__ x, i
                 if constexpr (EPI == 3) acc1 = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, f1[i], acc1, 0, 0, 0);
             }
         }
-        red_s[0][w][lane] = acc0;
-        if constexpr (EPI == 3) red_s[1][w][lane] = acc1;
-        __syncthreads();   // also: every wave is done with xs and rstd_s before the next slab overwrites them
-        if (w != 0 || n >= N) continue;   // wave 0 passes the next slab's barriers before red_s is rewritten
-        acc0 = ((red_s[0][0][lane] + red_s[0][1][lane]) + red_s[0][2][lane]) + red_s[0][3][lane];
-        if constexpr (EPI == 3) acc1 = ((red_s[1][0][lane] + red_s[1][1][lane]) + red_s[1][2][lane]) + red_s[1][3][lane];
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {   // D: column n = lane & 15, slab row (lane >> 4) * 4 + r
-            const int b = (lane >> 4) * 4 + r;
-            if (b >= nb) continue;
-            const size_t gr = (size_t)row0 + b;
-            if (ksplit == 1) {
-                float v = acc0[r];
-                if constexpr (EPI == 1) v += (float)extra[n];
-                if constexpr (EPI == 2) v += (float)extra[gr * N + n];
-                if constexpr (EPI == 3) v = silu_fast(acc0[r]) * acc1[r];
-                y[gr * N + n] = (bf16)v;
-            } else {
-                part[(((size_t)ks * NACC) * rows16 + gr) * N + n] = acc0[r];
-                if constexpr (EPI == 3) part[(((size_t)ks * NACC + 1) * rows16 + gr) * N + n] = acc1[r];
-            }
-        }
+        // the sum's barrier: every wave is done with xs and rstd_s before the next slab overwrites them, and
+        // wave 0 passes the next slab's barriers before red_s is rewritten
+        if (!gb_wave_order_sum(red_s, w, lane, acc0, acc1) || n >= N) continue;
+        gb_store<EPI>(acc0, acc1, lane, nb, row0, rows16, n, N, ks, ksplit, extra, y, part);
     }
-}
-
-// k_gemv_batch_reduce over `rows` rows of partials [ksplit, NACC, rows16, N]: grid (ceil(N / 256), rows).
-template <int EPI>
-__global__ void __launch_bounds__(NT) k_gemv_slabs_reduce(const float* __restrict__ part, const bf16* __restrict__ extra,
-                                                          bf16* __restrict__ y, int rows, int rows16, int N,
-                                                          int ksplit) {
-    constexpr int NACC = EPI == 3 ? 2 : 1;
-    const int b = blockIdx.y, n = blockIdx.x * NT + threadIdx.x;
-    if (b >= rows || n >= N) return;
-    float a0 = 0.f, a1 = 0.f;
-    for (int ks = 0; ks < ksplit; ++ks) {
-        a0 += part[(((size_t)ks * NACC) * rows16 + b) * N + n];
-        if constexpr (EPI == 3) a1 += part[(((size_t)ks * NACC + 1) * rows16 + b) * N + n];
-    }
-    float v = a0;
-    if constexpr (EPI == 1) v += (float)extra[n];
-    if constexpr (EPI == 2) v += (float)extra[(size_t)b * N + n];
-    if constexpr (EPI == 3) v = silu_fast(a0) * a1;
-    y[(size_t)b * N + n] = (bf16)v;
 }
 
 // Extend attention (kd_attn_extend): the ragged suffix rows of nb questions, each against its own
@@ -1007,6 +949,71 @@ static GemvBatchPlan gemv_batch_plan(int N, int K) {
     return p;
 }
 
+// f(std::integral_constant<int, E>) for the epilogue / head dim given at run time (both validated
+// by the caller): one place that turns the value into a template instance.
+template <typename F>
+static void dispatch_epi(int epi, F&& f) {
+    switch (epi) {
+        case 0: f(std::integral_constant<int, 0>{}); break;
+        case 1: f(std::integral_constant<int, 1>{}); break;
+        case 2: f(std::integral_constant<int, 2>{}); break;
+        default: f(std::integral_constant<int, 3>{});
+    }
+}
+template <typename F>
+static void dispatch_hd(int hd, F&& f) {
+    if (hd == 64) f(std::integral_constant<int, 64>{});
+    else f(std::integral_constant<int, 128>{});
+}
+
+// The argument checks of kd_gemv (rows_msg == nullptr: one row, read by scalar loads, no ldx) and
+// of kd_gemv_batch / kd_gemv_rows (1 <= rows <= rows_max, else rows_msg), in the order the ABI
+// tests pin; `who` names the entry in every message.
+static int check_gemv_args(const char* who, const void* x, int64_t ldx, int rows, int rows_max, const char* rows_msg,
+                           const void* W, int64_t ldw, const void* extra, const void* y, int N, int K, int epi, int I,
+                           const void* norm_w) {
+    auto msg = [who](const char* what) { return std::string(who) + ": " + what; };
+    KD_CHECK_ARG(x && W && y, msg("null pointer"));
+    KD_CHECK_ARG(epi >= 0 && epi <= 3 && (epi == 0 || epi == 3 || extra), msg("epilogue 0..3 (1, 2 need extra)"));
+    const bool k_ok = N > 0 && K > 0 && K % 8 == 0 && K <= 16384 && ldw >= K && ldw % 8 == 0;
+    if (!rows_msg) {
+        KD_CHECK_SHAPE(k_ok, msg("K must be a multiple of 8 (<= 16384), ldw >= K and a multiple of 8"));
+        KD_CHECK_ALIGN(W, 16, msg("W misaligned"));
+        return KD_OK;
+    }
+    KD_CHECK_SHAPE(rows >= 1 && rows <= rows_max, msg(rows_msg));
+    KD_CHECK_SHAPE(k_ok && ldx >= K && ldx % 8 == 0,
+                   msg("K must be a multiple of 8 (<= 16384), ldw and ldx >= K and multiples of 8"));
+    KD_CHECK_SHAPE(epi != 3 || I >= N, msg("SwiGLU needs inter >= N"));
+    KD_CHECK_ALIGN(W, 16, msg("W misaligned"));
+    KD_CHECK_ALIGN(x, 16, msg("x misaligned"));
+    KD_CHECK_ALIGN(norm_w, 16, msg("norm_w misaligned"));
+    return KD_OK;
+}
+
+// The argument checks of the three attention entries, in the order the ABI tests pin: ptrs_ok (every
+// pointer the entry needs), rows_ok (its row-count rule, rows_msg), the head geometry, smax (with
+// n_ok and its message for the entry that takes a host length), the alignment of the operands read
+// 16 B at a time (vc and v_new only where the entry passes them) and the workspace.
+static int check_attn_args(const char* who, bool ptrs_ok, bool rows_ok, const char* rows_msg, int H, int HKV, int hd,
+                           int hdp, int smax, bool n_ok, const char* smax_msg, const void* q, const void* kc,
+                           const void* vc, const void* k_new, const void* v_new, size_t ws_bytes, size_t ws_need) {
+    auto msg = [who](const char* what) { return std::string(who) + ": " + what; };
+    KD_CHECK_ARG(ptrs_ok, msg("null pointer"));
+    KD_CHECK_SHAPE(rows_ok, msg(rows_msg));
+    KD_CHECK_SHAPE(hd == 64 || hd == 128, msg("head dim must be 64 or 128"));
+    KD_CHECK_SHAPE(hdp >= hd && hdp % 8 == 0, msg("hdp must be >= hd and a multiple of 8"));
+    KD_CHECK_SHAPE(H > 0 && HKV > 0 && H % HKV == 0, msg("heads must be a multiple of kv heads"));
+    KD_CHECK_SHAPE(smax > 0 && smax <= MAX_CH * CH && n_ok, msg(smax_msg));
+    KD_CHECK_ALIGN(q, 16, msg("q misaligned"));
+    KD_CHECK_ALIGN(kc, 16, msg("k cache misaligned"));
+    KD_CHECK_ALIGN(vc, 16, msg("v cache misaligned"));
+    KD_CHECK_ALIGN(k_new, 16, msg("k_new misaligned"));
+    KD_CHECK_ALIGN(v_new, 16, msg("v_new misaligned"));
+    if (ws_bytes < ws_need) return fail(KD_ERR_WORKSPACE, msg("workspace too small"));
+    return KD_OK;
+}
+
 size_t gemv_batch_ws(int N, int K, int epi) {
     if (N <= 0 || K <= 0) return 0;
     const GemvBatchPlan p = gemv_batch_plan(N, K);
@@ -1015,42 +1022,31 @@ size_t gemv_batch_ws(int N, int K, int epi) {
 
 int launch_gemv_batch(const void* x, int64_t ldx, int nb, const void* W, int64_t ldw, const void* extra, void* y, int N,
                       int K, int epi, int I, const void* norm_w, float eps, void* ws, size_t ws_bytes, void* stream) {
-    KD_CHECK_ARG(x && W && y, "gemv_batch: null pointer");
-    KD_CHECK_ARG(epi >= 0 && epi <= 3 && (epi == 0 || epi == 3 || extra), "gemv_batch: epilogue 0..3 (1, 2 need extra)");
-    KD_CHECK_SHAPE(nb >= 1 && nb <= GB_ROWS, "gemv_batch: 1 <= nb <= 16");
-    KD_CHECK_SHAPE(N > 0 && K > 0 && K % 8 == 0 && K <= 16384 && ldw >= K && ldw % 8 == 0 && ldx >= K && ldx % 8 == 0,
-                   "gemv_batch: K must be a multiple of 8 (<= 16384), ldw and ldx >= K and multiples of 8");
-    KD_CHECK_SHAPE(epi != 3 || I >= N, "gemv_batch: SwiGLU needs inter >= N");
-    KD_CHECK_ALIGN(W, 16, "gemv_batch: W misaligned");
-    KD_CHECK_ALIGN(x, 16, "gemv_batch: x misaligned");
-    KD_CHECK_ALIGN(norm_w, 16, "gemv_batch: norm_w misaligned");
+    if (int rc = check_gemv_args("gemv_batch", x, ldx, nb, GB_ROWS, "1 <= nb <= 16", W, ldw, extra, y, N, K, epi, I,
+                                 norm_w))
+        return rc;
     const GemvBatchPlan p = gemv_batch_plan(N, K);
     if (p.ksplit > 1 && (!ws || ws_bytes < gemv_batch_ws(N, K, epi)))
         return fail(KD_ERR_WORKSPACE, "gemv_batch: workspace too small (kd_gemv_batch_workspace_size)");
-    const dim3 grid(p.wg_n, p.ksplit), rgrid((N + NT - 1) / NT, GB_ROWS);
+    const dim3 grid(p.wg_n, p.ksplit), rgrid((N + NT - 1) / NT, GB_ROWS);   // fixed by (N, K): rows >= nb exit
     const size_t lds = (size_t)GB_ROWS * (p.slice_steps * 32 + GB_PAD) * sizeof(bf16);
     hipStream_t s = as_stream(stream);
     const bf16 *xb = (const bf16*)x, *Wb = (const bf16*)W, *eb = (const bf16*)extra, *nw = (const bf16*)norm_w;
-#define KD_GB(E)                                                                                                       \
-    do {                                                                                                               \
-        hipLaunchKernelGGL(k_gemv_batch<E>, grid, dim3(NT), lds, s, xb, ldx, Wb, ldw, eb, (bf16*)y, (float*)ws, nb, N, \
-                           K, I, nw, eps, p.wave_n, p.slice_steps, p.ksplit);                                          \
-        if (p.ksplit > 1)                                                                                              \
-            hipLaunchKernelGGL(k_gemv_batch_reduce<E>, rgrid, dim3(NT), 0, s, (const float*)ws, eb, (bf16*)y, nb, N,   \
-                               p.ksplit);                                                                              \
-    } while (0)
-    switch (epi) {
-        case 0: KD_GB(0); break;
-        case 1: KD_GB(1); break;
-        case 2: KD_GB(2); break;
-        default: KD_GB(3);
-    }
-#undef KD_GB
+    dispatch_epi(epi, [&](auto e) {
+        constexpr int E = decltype(e)::value;
+        hipLaunchKernelGGL(k_gemv_batch<E>, grid, dim3(NT), lds, s, xb, ldx, Wb, ldw, eb, (bf16*)y, (float*)ws, nb, N, K,
+                           I, nw, eps, p.wave_n, p.slice_steps, p.ksplit);
+        if (p.ksplit > 1)
+            hipLaunchKernelGGL(k_gemv_batch_reduce<E>, rgrid, dim3(NT), 0, s, (const float*)ws, eb, (bf16*)y, nb,
+                               GB_ROWS, N, p.ksplit);
+    });
     KD_LAUNCH_CHECK("k_gemv_batch");
     return KD_OK;
 }
 
-size_t attn_decode_ws(int H, int hd, int smax);
+size_t attn_decode_ws(int H, int hd, int smax) {
+    return (size_t)H * ((smax + CH - 1) / CH) * (hd + 2) * sizeof(float);
+}
 
 size_t attn_decode_batch_ws(int nb, int H, int hd, int smax) {
     return (size_t)std::max(nb, 0) * attn_decode_ws(H, hd, smax);
@@ -1059,32 +1055,22 @@ size_t attn_decode_batch_ws(int nb, int H, int hd, int smax) {
 int launch_attn_decode_batch(const void* q, const void* k_new, const void* v_new, void* kc, void* vc, void* o, int nb,
                              int H, int HKV, int hd, int hdp, int smax, const int* cur_dev, void* ws, size_t ws_bytes,
                              void* stream) {
-    KD_CHECK_ARG(q && k_new && v_new && kc && vc && o && cur_dev && ws, "attn_decode_batch: null pointer");
-    KD_CHECK_SHAPE(nb >= 1 && nb <= GB_ROWS, "attn_decode_batch: 1 <= nb <= 16");
-    KD_CHECK_SHAPE(hd == 64 || hd == 128, "attn_decode_batch: head dim must be 64 or 128");
-    KD_CHECK_SHAPE(hdp >= hd && hdp % 8 == 0, "attn_decode_batch: hdp must be >= hd and a multiple of 8");
-    KD_CHECK_SHAPE(H > 0 && HKV > 0 && H % HKV == 0, "attn_decode_batch: heads must be a multiple of kv heads");
-    KD_CHECK_SHAPE(smax > 0 && smax <= MAX_CH * CH, "attn_decode_batch: need 0 < smax <= 32768");
-    KD_CHECK_ALIGN(q, 16, "attn_decode_batch: q misaligned");
-    KD_CHECK_ALIGN(kc, 16, "attn_decode_batch: k cache misaligned");
-    KD_CHECK_ALIGN(k_new, 16, "attn_decode_batch: k_new misaligned");
-    if (ws_bytes < attn_decode_batch_ws(nb, H, hd, smax))
-        return fail(KD_ERR_WORKSPACE, "attn_decode_batch: workspace too small");
+    if (int rc = check_attn_args("attn_decode_batch", q && k_new && v_new && kc && vc && o && cur_dev && ws,
+                                 nb >= 1 && nb <= GB_ROWS, "1 <= nb <= 16", H, HKV, hd, hdp, smax, true,
+                                 "need 0 < smax <= 32768", q, kc, nullptr, k_new, nullptr, ws_bytes,
+                                 attn_decode_batch_ws(nb, H, hd, smax)))
+        return rc;
     const int nch = (smax + CH - 1) / CH, ngrp = (H / HKV + AB_R - 1) / AB_R;   // head groups per kv head
     const float scale = 1.0f / sqrtf((float)hd);
     hipStream_t s = as_stream(stream);
     float* part = (float*)ws;
-    if (hd == 64) {
-        hipLaunchKernelGGL(k_attn_decode_part_batch<64>, dim3(HKV * ngrp, nch, nb), dim3(NT), 0, s, (const bf16*)q,
+    dispatch_hd(hd, [&](auto d) {
+        constexpr int HD = decltype(d)::value;
+        hipLaunchKernelGGL(k_attn_decode_part_batch<HD>, dim3(HKV * ngrp, nch, nb), dim3(NT), 0, s, (const bf16*)q,
                            (const bf16*)k_new, (const bf16*)v_new, (bf16*)kc, (bf16*)vc, part, H, HKV, hdp, smax, nb,
                            cur_dev, scale);
-        hipLaunchKernelGGL(k_attn_decode_combine<64>, dim3(nb * H), dim3(NT), 0, s, part, nch, (bf16*)o);
-    } else {
-        hipLaunchKernelGGL(k_attn_decode_part_batch<128>, dim3(HKV * ngrp, nch, nb), dim3(NT), 0, s, (const bf16*)q,
-                           (const bf16*)k_new, (const bf16*)v_new, (bf16*)kc, (bf16*)vc, part, H, HKV, hdp, smax, nb,
-                           cur_dev, scale);
-        hipLaunchKernelGGL(k_attn_decode_combine<128>, dim3(nb * H), dim3(NT), 0, s, part, nch, (bf16*)o);
-    }
+        hipLaunchKernelGGL(k_attn_decode_combine<HD>, dim3(nb * H), dim3(NT), 0, s, part, nch, (bf16*)o);
+    });
     KD_LAUNCH_CHECK("k_attn_decode_batch");
     return KD_OK;
 }
@@ -1099,15 +1085,9 @@ size_t gemv_rows_ws(int rows, int N, int K, int epi) {
 
 int launch_gemv_rows(const void* x, int64_t ldx, int rows, const void* W, int64_t ldw, const void* extra, void* y, int N,
                      int K, int epi, int I, const void* norm_w, float eps, void* ws, size_t ws_bytes, void* stream) {
-    KD_CHECK_ARG(x && W && y, "gemv_rows: null pointer");
-    KD_CHECK_ARG(epi >= 0 && epi <= 3 && (epi == 0 || epi == 3 || extra), "gemv_rows: epilogue 0..3 (1, 2 need extra)");
-    KD_CHECK_SHAPE(rows >= 1 && rows <= KD_GEMV_ROWS_MAX, "gemv_rows: 1 <= rows <= KD_GEMV_ROWS_MAX");
-    KD_CHECK_SHAPE(N > 0 && K > 0 && K % 8 == 0 && K <= 16384 && ldw >= K && ldw % 8 == 0 && ldx >= K && ldx % 8 == 0,
-                   "gemv_rows: K must be a multiple of 8 (<= 16384), ldw and ldx >= K and multiples of 8");
-    KD_CHECK_SHAPE(epi != 3 || I >= N, "gemv_rows: SwiGLU needs inter >= N");
-    KD_CHECK_ALIGN(W, 16, "gemv_rows: W misaligned");
-    KD_CHECK_ALIGN(x, 16, "gemv_rows: x misaligned");
-    KD_CHECK_ALIGN(norm_w, 16, "gemv_rows: norm_w misaligned");
+    if (int rc = check_gemv_args("gemv_rows", x, ldx, rows, KD_GEMV_ROWS_MAX, "1 <= rows <= KD_GEMV_ROWS_MAX", W, ldw,
+                                 extra, y, N, K, epi, I, norm_w))
+        return rc;
     const GemvBatchPlan p = gemv_batch_plan(N, K);
     if (p.ksplit > 1 && (!ws || ws_bytes < gemv_rows_ws(rows, N, K, epi)))
         return fail(KD_ERR_WORKSPACE, "gemv_rows: workspace too small (kd_gemv_rows_workspace_size)");
@@ -1127,21 +1107,14 @@ int launch_gemv_rows(const void* x, int64_t ldx, int rows, const void* W, int64_
     const dim3 grid(p.wg_n, p.ksplit, std::min(rows16 / GB_ROWS, GS_SLAB_GROUPS)), rgrid((N + NT - 1) / NT, rows);
     const size_t lds = (size_t)GB_ROWS * (p.slice_steps * 32 + GB_PAD) * sizeof(bf16);
     hipStream_t s = as_stream(stream);
-#define KD_GS(E)                                                                                                       \
-    do {                                                                                                               \
-        hipLaunchKernelGGL(k_gemv_slabs<E>, grid, dim3(NT), lds, s, xb, ldx, Wb, ldw, eb, (bf16*)y, (float*)ws, rows,  \
-                           N, K, I, nw, eps, p.slice_steps, p.ksplit);                                                 \
-        if (p.ksplit > 1)                                                                                              \
-            hipLaunchKernelGGL(k_gemv_slabs_reduce<E>, rgrid, dim3(NT), 0, s, (const float*)ws, eb, (bf16*)y, rows,    \
-                               rows16, N, p.ksplit);                                                                   \
-    } while (0)
-    switch (epi) {
-        case 0: KD_GS(0); break;
-        case 1: KD_GS(1); break;
-        case 2: KD_GS(2); break;
-        default: KD_GS(3);
-    }
-#undef KD_GS
+    dispatch_epi(epi, [&](auto e) {
+        constexpr int E = decltype(e)::value;
+        hipLaunchKernelGGL(k_gemv_slabs<E>, grid, dim3(NT), lds, s, xb, ldx, Wb, ldw, eb, (bf16*)y, (float*)ws, rows, N, K,
+                           I, nw, eps, p.slice_steps, p.ksplit);
+        if (p.ksplit > 1)
+            hipLaunchKernelGGL(k_gemv_batch_reduce<E>, rgrid, dim3(NT), 0, s, (const float*)ws, eb, (bf16*)y, rows,
+                               rows16, N, p.ksplit);
+    });
     KD_LAUNCH_CHECK("k_gemv_slabs");
     return KD_OK;
 }
@@ -1153,34 +1126,23 @@ size_t attn_extend_ws(int rows, int H, int hd, int smax) {
 int launch_attn_extend(const void* q, const void* k_new, const void* v_new, void* kc, void* vc, void* o, int nb,
                        int rows, int H, int HKV, int hd, int hdp, int smax, const int* row_start, const int* base,
                        void* ws, size_t ws_bytes, void* stream) {
-    KD_CHECK_ARG(q && k_new && v_new && kc && vc && o && row_start && base && ws, "attn_extend: null pointer");
-    KD_CHECK_SHAPE(rows >= 1 && rows <= KD_GEMV_ROWS_MAX && nb >= 1 && nb <= rows,
-                   "attn_extend: 1 <= nb <= rows <= KD_GEMV_ROWS_MAX");
-    KD_CHECK_SHAPE(hd == 64 || hd == 128, "attn_extend: head dim must be 64 or 128");
-    KD_CHECK_SHAPE(hdp >= hd && hdp % 8 == 0, "attn_extend: hdp must be >= hd and a multiple of 8");
-    KD_CHECK_SHAPE(H > 0 && HKV > 0 && H % HKV == 0, "attn_extend: heads must be a multiple of kv heads");
-    KD_CHECK_SHAPE(smax > 0 && smax <= MAX_CH * CH, "attn_extend: need 0 < smax <= 32768");
-    KD_CHECK_ALIGN(q, 16, "attn_extend: q misaligned");
-    KD_CHECK_ALIGN(kc, 16, "attn_extend: k cache misaligned");
-    KD_CHECK_ALIGN(vc, 16, "attn_extend: v cache misaligned");
-    KD_CHECK_ALIGN(k_new, 16, "attn_extend: k_new misaligned");
-    KD_CHECK_ALIGN(v_new, 16, "attn_extend: v_new misaligned");
-    if (ws_bytes < attn_extend_ws(rows, H, hd, smax)) return fail(KD_ERR_WORKSPACE, "attn_extend: workspace too small");
+    if (int rc = check_attn_args("attn_extend", q && k_new && v_new && kc && vc && o && row_start && base && ws,
+                                 rows >= 1 && rows <= KD_GEMV_ROWS_MAX && nb >= 1 && nb <= rows,
+                                 "1 <= nb <= rows <= KD_GEMV_ROWS_MAX", H, HKV, hd, hdp, smax, true,
+                                 "need 0 < smax <= 32768", q, kc, vc, k_new, v_new, ws_bytes,
+                                 attn_extend_ws(rows, H, hd, smax)))
+        return rc;
     const int nch = (smax + CH - 1) / CH;
     const float scale = 1.0f / sqrtf((float)hd);
     hipStream_t s = as_stream(stream);
     float* part = (float*)ws;
-    if (hd == 64) {
-        hipLaunchKernelGGL(k_attn_extend_part<64>, dim3(HKV, nch, nb), dim3(NT), 0, s, (const bf16*)q,
+    dispatch_hd(hd, [&](auto d) {
+        constexpr int HD = decltype(d)::value;
+        hipLaunchKernelGGL(k_attn_extend_part<HD>, dim3(HKV, nch, nb), dim3(NT), 0, s, (const bf16*)q,
                            (const bf16*)k_new, (const bf16*)v_new, (bf16*)kc, (bf16*)vc, part, H, HKV, hdp, smax, rows,
                            row_start, base, scale);
-        hipLaunchKernelGGL(k_attn_decode_combine<64>, dim3(rows * H), dim3(NT), 0, s, part, nch, (bf16*)o);
-    } else {
-        hipLaunchKernelGGL(k_attn_extend_part<128>, dim3(HKV, nch, nb), dim3(NT), 0, s, (const bf16*)q,
-                           (const bf16*)k_new, (const bf16*)v_new, (bf16*)kc, (bf16*)vc, part, H, HKV, hdp, smax, rows,
-                           row_start, base, scale);
-        hipLaunchKernelGGL(k_attn_decode_combine<128>, dim3(rows * H), dim3(NT), 0, s, part, nch, (bf16*)o);
-    }
+        hipLaunchKernelGGL(k_attn_decode_combine<HD>, dim3(rows * H), dim3(NT), 0, s, part, nch, (bf16*)o);
+    });
     KD_LAUNCH_CHECK("k_attn_extend");
     return KD_OK;
 }
@@ -1222,78 +1184,55 @@ int launch_gen_finish(const int64_t* tok, const int* cur_dev, int nb, const int6
     return KD_OK;
 }
 
+// One row of k_rope_rows; the table's length is not passed in, so only the lower clamp (a counter
+// of 0 reads row 0) is in force.
 int launch_rope_row(const float* cos_t, const float* sin_t, int hh, const int* cur_dev, float* cos_row, float* sin_row,
                     void* stream) {
     KD_CHECK_ARG(cos_t && sin_t && cur_dev && cos_row && sin_row, "rope_row: null pointer");
     KD_CHECK_SHAPE(hh > 0, "rope_row: hh must be positive");
-    hipLaunchKernelGGL(k_rope_row, dim3(1), dim3(256), 0, as_stream(stream), cos_t, sin_t, hh, cur_dev, cos_row,
+    hipLaunchKernelGGL(k_rope_rows, dim3(1), dim3(256), 0, as_stream(stream), cos_t, sin_t, hh, INT_MAX, cur_dev, cos_row,
                        sin_row);
-    KD_LAUNCH_CHECK("k_rope_row");
+    KD_LAUNCH_CHECK("k_rope_rows");
     return KD_OK;
-}
-
-size_t attn_decode_ws(int H, int hd, int smax) {
-    return (size_t)H * ((smax + CH - 1) / CH) * (hd + 2) * sizeof(float);
 }
 
 int launch_attn_decode(const void* q, const void* k_new, const void* v_new, void* kc, void* vc, void* o, int H,
                        int HKV, int hd, int hdp, int smax, int n, const int* cur_dev, void* ws, size_t ws_bytes,
                        void* stream) {
-    KD_CHECK_ARG(q && k_new && v_new && kc && vc && o && ws, "attn_decode: null pointer");
-    KD_CHECK_SHAPE(hd == 64 || hd == 128, "attn_decode: head dim must be 64 or 128");
-    KD_CHECK_SHAPE(hdp >= hd && hdp % 8 == 0, "attn_decode: hdp must be >= hd and a multiple of 8");
-    KD_CHECK_SHAPE(H > 0 && HKV > 0 && H % HKV == 0, "attn_decode: heads must be a multiple of kv heads");
-    KD_CHECK_SHAPE(smax > 0 && smax <= MAX_CH * CH && (cur_dev || (n > 0 && n <= smax)),
-                   "attn_decode: need 0 < n <= smax <= 32768");
-    KD_CHECK_ALIGN(q, 16, "attn_decode: q misaligned");
-    KD_CHECK_ALIGN(kc, 16, "attn_decode: k cache misaligned");
-    KD_CHECK_ALIGN(k_new, 16, "attn_decode: k_new misaligned");
-    if (ws_bytes < attn_decode_ws(H, hd, smax)) return fail(KD_ERR_WORKSPACE, "attn_decode: workspace too small");
+    if (int rc = check_attn_args("attn_decode", q && k_new && v_new && kc && vc && o && ws, true, "", H, HKV, hd, hdp,
+                                 smax, cur_dev || (n > 0 && n <= smax), "need 0 < n <= smax <= 32768", q, kc, nullptr,
+                                 k_new, nullptr, ws_bytes, attn_decode_ws(H, hd, smax)))
+        return rc;
     const int nch = (smax + CH - 1) / CH;
     const float scale = 1.0f / sqrtf((float)hd);
     hipStream_t s = as_stream(stream);
     float* part = (float*)ws;
-    if (hd == 64) {
-        hipLaunchKernelGGL(k_attn_decode_part<64>, dim3(H, nch), dim3(NT), 0, s, (const bf16*)q, (const bf16*)k_new,
+    dispatch_hd(hd, [&](auto d) {
+        constexpr int HD = decltype(d)::value;
+        hipLaunchKernelGGL(k_attn_decode_part<HD>, dim3(H, nch), dim3(NT), 0, s, (const bf16*)q, (const bf16*)k_new,
                            (const bf16*)v_new, (bf16*)kc, (bf16*)vc, part, H, HKV, hdp, smax, n, cur_dev, scale);
-        hipLaunchKernelGGL(k_attn_decode_combine<64>, dim3(H), dim3(NT), 0, s, part, nch, (bf16*)o);
-    } else {
-        hipLaunchKernelGGL(k_attn_decode_part<128>, dim3(H, nch), dim3(NT), 0, s, (const bf16*)q, (const bf16*)k_new,
-                           (const bf16*)v_new, (bf16*)kc, (bf16*)vc, part, H, HKV, hdp, smax, n, cur_dev, scale);
-        hipLaunchKernelGGL(k_attn_decode_combine<128>, dim3(H), dim3(NT), 0, s, part, nch, (bf16*)o);
-    }
+        hipLaunchKernelGGL(k_attn_decode_combine<HD>, dim3(H), dim3(NT), 0, s, part, nch, (bf16*)o);
+    });
     KD_LAUNCH_CHECK("k_attn_decode");
     return KD_OK;
 }
 
 int launch_gemv(const void* x, const void* W, int64_t ldw, const void* extra, void* y, int N, int K, int epi, int I,
                 const void* norm_w, float eps, void* stream) {
-    KD_CHECK_ARG(x && W && y, "gemv: null pointer");
-    KD_CHECK_ARG(epi >= 0 && epi <= 3 && (epi == 0 || epi == 3 || extra), "gemv: epilogue 0..3 (1, 2 need extra)");
-    KD_CHECK_SHAPE(N > 0 && K > 0 && K % 8 == 0 && K <= 16384 && ldw >= K && ldw % 8 == 0,
-                   "gemv: K must be a multiple of 8 (<= 16384), ldw >= K and a multiple of 8");
-    KD_CHECK_ALIGN(W, 16, "gemv: W misaligned");
-    const dim3 grid((N + NT / 64 - 1) / (NT / 64));
+    if (int rc = check_gemv_args("gemv", x, 0, 1, 1, nullptr, W, ldw, extra, y, N, K, epi, I, norm_w)) return rc;
     const size_t lds = (size_t)K * sizeof(float);
     hipStream_t s = as_stream(stream);
     const bf16 *xb = (const bf16*)x, *Wb = (const bf16*)W, *eb = (const bf16*)extra, *nw = (const bf16*)norm_w;
-    if (N < 4096 && K >= 512) {   // few rows: one workgroup per row, K split over 256 threads
-        switch (epi) {
-            case 0: hipLaunchKernelGGL(k_gemv_rows<0>, dim3(N), dim3(NT), lds, s, xb, Wb, ldw, eb, (bf16*)y, K, I, nw, eps); break;
-            case 1: hipLaunchKernelGGL(k_gemv_rows<1>, dim3(N), dim3(NT), lds, s, xb, Wb, ldw, eb, (bf16*)y, K, I, nw, eps); break;
-            case 2: hipLaunchKernelGGL(k_gemv_rows<2>, dim3(N), dim3(NT), lds, s, xb, Wb, ldw, eb, (bf16*)y, K, I, nw, eps); break;
-            default: hipLaunchKernelGGL(k_gemv_rows<3>, dim3(N), dim3(NT), lds, s, xb, Wb, ldw, eb, (bf16*)y, K, I, nw, eps);
-        }
-        KD_LAUNCH_CHECK("k_gemv_rows");
-        return KD_OK;
-    }
-    switch (epi) {
-        case 0: hipLaunchKernelGGL(k_gemv<0>, grid, dim3(NT), lds, s, xb, Wb, ldw, eb, (bf16*)y, N, K, I, nw, eps); break;
-        case 1: hipLaunchKernelGGL(k_gemv<1>, grid, dim3(NT), lds, s, xb, Wb, ldw, eb, (bf16*)y, N, K, I, nw, eps); break;
-        case 2: hipLaunchKernelGGL(k_gemv<2>, grid, dim3(NT), lds, s, xb, Wb, ldw, eb, (bf16*)y, N, K, I, nw, eps); break;
-        default: hipLaunchKernelGGL(k_gemv<3>, grid, dim3(NT), lds, s, xb, Wb, ldw, eb, (bf16*)y, N, K, I, nw, eps);
-    }
-    KD_LAUNCH_CHECK("k_gemv");
+    const bool wide = N < 4096 && K >= 512;   // few rows: one workgroup per row, K split over 256 threads
+    dispatch_epi(epi, [&](auto e) {
+        constexpr int E = decltype(e)::value;
+        if (wide)
+            hipLaunchKernelGGL(k_gemv_wide<E>, dim3(N), dim3(NT), lds, s, xb, Wb, ldw, eb, (bf16*)y, K, I, nw, eps);
+        else
+            hipLaunchKernelGGL(k_gemv<E>, dim3((N + NT / 64 - 1) / (NT / 64)), dim3(NT), lds, s, xb, Wb, ldw, eb,
+                               (bf16*)y, N, K, I, nw, eps);
+    });
+    KD_LAUNCH_CHECK(wide ? "k_gemv_wide" : "k_gemv");
     return KD_OK;
 }
 

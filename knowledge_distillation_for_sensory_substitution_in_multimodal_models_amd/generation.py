@@ -116,6 +116,68 @@ def _stats_chunk(stats, ran, n_steps, checks, finished_at):
         stats["finished_at"].append(finished_at)
 
 
+def _eos_set(eos_token_id) -> set:
+    return {int(e) for e in ([eos_token_id] if isinstance(eos_token_id, int) else (eos_token_id or ()))}
+
+
+def _decode_layers(model):
+    """Per layer: (input norm, q|k|v weight, q|k|v bias, o_proj, post-attention norm, gate|up, down)."""
+    T, P = model.cfg.text, model.P
+    qd, kd = T.heads * T.head_dim, T.kv_heads * T.head_dim
+    lp = "language_model.model."
+    layers = []
+    for i in range(T.layers):
+        p = f"{lp}layers.{i}."
+        layers.append((P[p + "input_layernorm.weight"],
+                       P.span(p + "self_attn.q_proj.weight", p + "self_attn.v_proj.weight", qd + 2 * kd, T.hidden),
+                       P.span(p + "self_attn.q_proj.bias", p + "self_attn.v_proj.bias", 1, qd + 2 * kd).view(-1),
+                       P[p + "self_attn.o_proj.weight"], P[p + "post_attention_layernorm.weight"],
+                       P.span(p + "mlp.gate_proj.weight", p + "mlp.up_proj.weight", 2 * T.inter, T.hidden),
+                       P[p + "mlp.down_proj.weight"]))
+    return layers
+
+
+def _run_steps(step, n_steps: int, graph: bool, stop: _Stop, on_logits=None) -> int:
+    """The decode loop of every entry point: step() (one token for every row; returns its logits) up
+    to n_steps times, the first eagerly (warm-up: allocations, workspaces), the rest as replays of
+    one HIP graph captured at the second; on_logits(lg) after each (lg is the graph's static buffer:
+    clone what is kept); ends early once stop.done().  -> the steps run."""
+    graph_obj, ran = None, 0
+    for t_ in range(n_steps):
+        if graph and t_ == 1:
+            graph_obj = torch.cuda.CUDAGraph()
+            with torch.cuda.graph(graph_obj):
+                lg_static = step()
+        if graph_obj is not None:
+            graph_obj.replay()
+            lg = lg_static
+        else:
+            lg = step()
+        if on_logits is not None:
+            on_logits(lg)
+        ran = t_ + 1
+        if stop.done(ran, n_steps):
+            break
+    return ran
+
+
+def _first_eos(stop: _Stop, seq, Ls, max_new_tokens: int, eos) -> list:
+    """Per row of seq [nb, smax] the length at its first EOS among its new tokens (0: none), where
+    transformers stops; the steps past it are discarded.  Kept by the device when the stop is active
+    (after an early stop the positions past it were never written), else one scan on the host."""
+    fin = stop.ends()
+    if fin is None:
+        fin = [0] * len(Ls)
+        if eos:
+            host = seq.tolist()
+            for b, L in enumerate(Ls):
+                for j, t_ in enumerate(host[b][L:L + max_new_tokens]):
+                    if t_ in eos:
+                        fin[b] = L + j + 1
+                        break
+    return fin
+
+
 @torch.no_grad()
 def generate(model, input_ids: torch.Tensor, pixel_values: torch.Tensor, image_sizes, max_new_tokens: int = 32,
              repetition_penalty: float = 1.0, no_repeat_ngram_size: int = 0, eos_token_id=EOS_TOKEN_IDS,
@@ -141,9 +203,8 @@ def generate(model, input_ids: torch.Tensor, pixel_values: torch.Tensor, image_s
     dev = model.device
     L = int(input_ids.shape[1])
     smax = L + int(max_new_tokens)
-    eos = {int(e) for e in ([eos_token_id] if isinstance(eos_token_id, int) else (eos_token_id or ()))}
+    eos = _eos_set(eos_token_id)
     nq, nkv, hd = T.heads, T.kv_heads, T.head_dim
-    qd, kd = nq * hd, nkv * hd
     lp = "language_model.model."
 
     # ---- prefill: the training forward, its roped k/v kept
@@ -165,15 +226,7 @@ def generate(model, input_ids: torch.Tensor, pixel_values: torch.Tensor, image_s
     cos, sin = model._rope_for(smax)
     src = torch.full((1,), -2, dtype=torch.int32, device=dev)   # token embedding (kd_embed_assemble)
     table = P[lp + "embed_tokens.weight"]
-    layers = []
-    for i in range(T.layers):
-        p = f"{lp}layers.{i}."
-        layers.append((P[p + "input_layernorm.weight"],
-                       P.span(p + "self_attn.q_proj.weight", p + "self_attn.v_proj.weight", qd + 2 * kd, T.hidden),
-                       P.span(p + "self_attn.q_proj.bias", p + "self_attn.v_proj.bias", 1, qd + 2 * kd).view(-1),
-                       P[p + "self_attn.o_proj.weight"], P[p + "post_attention_layernorm.weight"],
-                       P.span(p + "mlp.gate_proj.weight", p + "mlp.up_proj.weight", 2 * T.inter, T.hidden),
-                       P[p + "mlp.down_proj.weight"]))
+    layers = _decode_layers(model)
     # device-resident step state: the sequence length (tokens so far, the one being decoded
     # included), the token being decoded and its RoPE row -> every launch of a step has fixed
     # arguments and the step replays from one captured HIP graph
@@ -211,33 +264,8 @@ def generate(model, input_ids: torch.Tensor, pixel_values: torch.Tensor, image_s
         return lg
 
     n_steps = smax - (L + 1)
-    graph_obj = None
-    ran = 0
-    for t_ in range(n_steps):
-        if graph and t_ == 1:   # step 0 ran eagerly (warm-up: allocations, workspaces); capture the rest
-            graph_obj = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(graph_obj):
-                lg_static = step()
-        if graph_obj is not None:
-            graph_obj.replay()
-            lg = lg_static
-        else:
-            lg = step()
-        if return_logits:
-            steps.append(lg.clone())
-        ran = t_ + 1
-        if stop.done(ran, n_steps):
-            break
-    end = 0   # the length at the first EOS (0: none); transformers stops there, the steps past it are discarded
-    fin = stop.ends()
-    if fin is not None:   # kept by the device (after an early stop the positions past it were never written)
-        end = fin[0]
-    elif eos:
-        gen = seq[L:smax].tolist()
-        for j, t_ in enumerate(gen):
-            if t_ in eos:
-                end = L + j + 1
-                break
+    ran = _run_steps(step, n_steps, graph, stop, (lambda lg: steps.append(lg.clone())) if return_logits else None)
+    end = _first_eos(stop, seq.view(1, smax), [L], int(max_new_tokens), eos)[0]
     n = end or smax
     if return_logits:
         steps = steps[:n - L]
@@ -297,7 +325,7 @@ def _generate_rows(model, prompts, max_new_tokens, repetition_penalty, no_repeat
     nb = len(prompts)
     Ls = [int(ids.shape[1]) for ids, _, _ in prompts]
     smax = max(Ls) + max_new_tokens
-    eos = {int(e) for e in ([eos_token_id] if isinstance(eos_token_id, int) else (eos_token_id or ()))}
+    eos = _eos_set(eos_token_id)
     nkv, hd = T.kv_heads, T.head_dim
 
     # ---- prefill, one prompt at a time: generate()'s own (row b of the caches and of seq)
@@ -322,23 +350,6 @@ def _generate_rows(model, prompts, max_new_tokens, repetition_penalty, no_repeat
 
     return _decode_rows(model, kc, vc, seq, Ls, steps, max_new_tokens, repetition_penalty, no_repeat_ngram_size, eos,
                         return_logits, graph, k_stop, stats)
-
-
-def _decode_layers(model):
-    """Per layer: (input norm, q|k|v weight, q|k|v bias, o_proj, post-attention norm, gate|up, down)."""
-    T, P = model.cfg.text, model.P
-    qd, kd = T.heads * T.head_dim, T.kv_heads * T.head_dim
-    lp = "language_model.model."
-    layers = []
-    for i in range(T.layers):
-        p = f"{lp}layers.{i}."
-        layers.append((P[p + "input_layernorm.weight"],
-                       P.span(p + "self_attn.q_proj.weight", p + "self_attn.v_proj.weight", qd + 2 * kd, T.hidden),
-                       P.span(p + "self_attn.q_proj.bias", p + "self_attn.v_proj.bias", 1, qd + 2 * kd).view(-1),
-                       P[p + "self_attn.o_proj.weight"], P[p + "post_attention_layernorm.weight"],
-                       P.span(p + "mlp.gate_proj.weight", p + "mlp.up_proj.weight", 2 * T.inter, T.hidden),
-                       P[p + "mlp.down_proj.weight"]))
-    return layers
 
 
 def _decode_rows(model, kc, vc, seq, Ls, steps, max_new_tokens, repetition_penalty, no_repeat_ngram_size, eos,
@@ -379,36 +390,15 @@ def _decode_rows(model, kc, vc, seq, Ls, steps, max_new_tokens, repetition_penal
         stop.mark(tok, cur)
         return lg
 
-    graph_obj = None
-    n_steps, ran = max_new_tokens - 1, 0
-    for t_ in range(n_steps):
-        if graph and t_ == 1:   # step 0 ran eagerly (warm-up: allocations, workspaces); capture the rest
-            graph_obj = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(graph_obj):
-                lg_static = step()
-        if graph_obj is not None:
-            graph_obj.replay()
-            lg = lg_static
-        else:
-            lg = step()
-        if return_logits:
-            lg = lg.clone()
-            for b in range(nb):
-                steps[b].append(lg[b:b + 1])
-        ran = t_ + 1
-        if stop.done(ran, n_steps):
-            break
-    # every row is cut after its own first EOS (fin[b]: its length there, 0 if none); the steps past it are discarded
-    fin = stop.ends()
-    if fin is None:
-        fin = [0] * nb
-        if eos:
-            host = seq.tolist()
-            for b, L in enumerate(Ls):
-                for j, t_ in enumerate(host[b][L:L + max_new_tokens]):
-                    if t_ in eos:
-                        fin[b] = L + j + 1
-                        break
+    def keep(lg):
+        lg = lg.clone()
+        for b in range(nb):
+            steps[b].append(lg[b:b + 1])
+
+    n_steps = max_new_tokens - 1
+    ran = _run_steps(step, n_steps, graph, stop, keep if return_logits else None)
+    # every row is cut after its own first EOS (fin[b]: its length there, 0 if none)
+    fin = _first_eos(stop, seq, Ls, max_new_tokens, eos)
     ends = [fin[b] or L + max_new_tokens for b, L in enumerate(Ls)]
     for b, L in enumerate(Ls):
         steps[b] = steps[b][:ends[b] - L]
@@ -493,7 +483,7 @@ def _generate_grouped_rows(model, chunk, carry, max_new_tokens, repetition_penal
     Ls = [int(ids.shape[1]) for _, _, _, ids, _ in chunk]
     P0s = [P0 for *_, P0 in chunk]
     smax = max(Ls) + max_new_tokens
-    eos = {int(e) for e in ([eos_token_id] if isinstance(eos_token_id, int) else (eos_token_id or ()))}
+    eos = _eos_set(eos_token_id)
     nq, nkv, hd = T.heads, T.kv_heads, T.head_dim
     lp = "language_model.model."
 

@@ -737,21 +737,28 @@ def attn_decode(q: torch.Tensor, k_new: torch.Tensor, v_new: torch.Tensor, k_cac
     return out
 
 
+def _gemv_epilogue(w, bias, residual, swiglu_inter, rows, who=None):
+    """-> (epi, extra, N) of the decode GEMVs: 3 SwiGLU (w = gate|up, N = inter), 1 bias, 2 residual, 0
+    none.  who = (entry, its name for the row count): the residual must be a contiguous [rows, N]."""
+    if swiglu_inter:
+        return 3, None, int(swiglu_inter)
+    N = w.shape[0]
+    if bias is not None:
+        return 1, bias, N
+    if residual is not None:
+        if who is not None and (residual.shape != (rows, N) or not residual.is_contiguous()):
+            raise RuntimeError(f"{who[0]}: residual must be a contiguous [{who[1]}, N] tensor")
+        return 2, residual, N
+    return 0, None, N
+
+
 def gemv(x: torch.Tensor, w: torch.Tensor, *, bias=None, residual=None, swiglu_inter: int = 0, norm_w=None,
          eps: float = 1e-6) -> torch.Tensor:
     """One token row through a linear layer (kd_gemv): x [1, K] bf16, w [N, K] (row stride may
     exceed K) -> [1, N] bf16 with an optional bias / residual / SwiGLU (w = gate|up, N = 2*inter),
     and with norm_w the RMSNorm of x fused in front."""
     K = x.shape[-1]
-    epi, extra = 0, None
-    if swiglu_inter:
-        epi, N = 3, int(swiglu_inter)
-    else:
-        N = w.shape[0]
-        if bias is not None:
-            epi, extra = 1, bias
-        elif residual is not None:
-            epi, extra = 2, residual
+    epi, extra, N = _gemv_epilogue(w, bias, residual, swiglu_inter, 1)
     y = torch.empty((1, N), dtype=torch.bfloat16, device=x.device)
     NV.call("kd_gemv", x.data_ptr(), w.data_ptr(), w.stride(0), _ptr(extra), y.data_ptr(), N, K, epi,
             int(swiglu_inter), _ptr(norm_w), float(eps), _stream())
@@ -796,17 +803,7 @@ def gemv_batch(x: torch.Tensor, w: torch.Tensor, *, bias=None, residual=None, sw
     if x.dim() != 2 or x.stride(1) != 1:
         raise RuntimeError("gemv_batch: x must be [nb, K] with a contiguous last dim")
     nb, K = x.shape
-    epi, extra = 0, None
-    if swiglu_inter:
-        epi, N = 3, int(swiglu_inter)
-    else:
-        N = w.shape[0]
-        if bias is not None:
-            epi, extra = 1, bias
-        elif residual is not None:
-            epi, extra = 2, residual
-            if residual.shape != (nb, N) or not residual.is_contiguous():
-                raise RuntimeError("gemv_batch: residual must be a contiguous [nb, N] tensor")
+    epi, extra, N = _gemv_epilogue(w, bias, residual, swiglu_inter, nb, ("gemv_batch", "nb"))
     y = torch.empty((nb, N), dtype=torch.bfloat16, device=x.device)
     nbytes = NV.lib().kd_gemv_batch_workspace_size(N, K, epi)
     ws = _workspace(("gemv_batch", _stream()), nbytes, x.device) if nbytes else None
@@ -889,17 +886,7 @@ def gemv_rows(x: torch.Tensor, w: torch.Tensor, *, bias=None, residual=None, swi
     if x.dim() != 2 or x.stride(1) != 1:
         raise RuntimeError("gemv_rows: x must be [rows, K] with a contiguous last dim")
     rows, K = x.shape
-    epi, extra = 0, None
-    if swiglu_inter:
-        epi, N = 3, int(swiglu_inter)
-    else:
-        N = w.shape[0]
-        if bias is not None:
-            epi, extra = 1, bias
-        elif residual is not None:
-            epi, extra = 2, residual
-            if residual.shape != (rows, N) or not residual.is_contiguous():
-                raise RuntimeError("gemv_rows: residual must be a contiguous [rows, N] tensor")
+    epi, extra, N = _gemv_epilogue(w, bias, residual, swiglu_inter, rows, ("gemv_rows", "rows"))
     if out is None:
         out = torch.empty((rows, N), dtype=torch.bfloat16, device=x.device)
     elif out.shape != (rows, N) or out.dtype != torch.bfloat16 or not out.is_contiguous():

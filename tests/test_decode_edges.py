@@ -40,10 +40,11 @@ A. kd_attn_decode / kd_attn_decode_batch / kd_attn_extend against an fp64 refere
 
 B. kd_gen_select / kd_gen_select_batch == oracle.generation.select on the bf16-rounded scores, at
    the vector tails, unaligned rows, planted and processor-made ties, all -inf rows, sequence
-   lengths around ngram and past the 1024-thread trip, and a full row (cur == smax).
+   lengths around ngram and past the 1024-thread trip, and a full row (cur == smax); kd_gen_select
+   == kd_gen_select_batch on the same row (token, written position, counter), alone and among others.
 
 C. kd_rope_row / kd_rope_rows copy exactly table row pos - 1 (clamped into the table for the
-   batched form) and write nothing outside their destination.
+   batched form) and write nothing outside their destination; kd_rope_row == row 0 of kd_rope_rows.
 
 """
 import functools
@@ -784,6 +785,49 @@ def test_gpu_gen_select_batch_full_row(dev):
     assert _select_batch(ops, dev, rows, smax, 1.2, 2, 1) == [61, 60, 61]
 
 
+@pytest.mark.gpu
+def test_gpu_gen_select_is_gen_select_batch_on_its_row(dev):
+    """V = 8197, penalty 1.2, ngram 2: kd_gen_select (device counter) on a row leaves exactly what
+    kd_gen_select_batch leaves for that row at nb = 1 and as row 1 of an nb = 3 call with ragged
+    lengths (where its logits and flags rows are unaligned): the token in out, the id written at
+    seq[len], nothing else of seq, and cur = len + 1.  The row's winner is seen (penalised below the
+    runner-up) and the runner-up is banned by its bigram, so both processors decide the result."""
+    ops = _ops()
+    V, smax, g = 8197, 64, np.random.default_rng(12)
+    lg = _scores(V, 31)
+    lg[4099], lg[8196], lg[17] = 30.0, 29.0, 24.5   # 30 / 1.2 = 25 < 29; 8196 banned -> 25 at 4099 beats 24.5
+    x = 7001
+    row = [int(t) for t in g.integers(100, 4000, 20)] + [4099, x, 8196] + [int(t) for t in g.integers(100, 4000, 9)] + [x]
+    others = ([int(t) for t in g.integers(0, V, 5)], [int(t) for t in g.integers(0, V, 47)])
+    want = G.select(lg.float().numpy(), row, 1.2, 2)
+    assert want == 4099
+
+    def single():
+        s = torch.full((smax,), -1, dtype=torch.int64)
+        s[:len(row)] = torch.tensor(row)
+        s, out = s.to(dev), torch.full((1,), -1, dtype=torch.int64, device=dev)
+        cur = torch.tensor([len(row)], dtype=torch.int32, device=dev)
+        ops.gen_select(lg.to(dev)[None], s, 0, 1.2, 2, out=out, cur=cur)
+        return int(out), s.cpu(), int(cur)
+
+    def batch(rows, b):
+        nb = len(rows)
+        s = torch.full((nb, smax), -1, dtype=torch.int64)
+        logits = torch.stack([_scores(V, 90 + i) for i in range(nb)])
+        logits[b] = lg
+        for i, sq in enumerate(rows):
+            s[i, :len(sq)] = torch.tensor(sq)
+        s, out = s.to(dev), torch.full((nb,), -1, dtype=torch.int64, device=dev)
+        cur = torch.tensor([len(sq) for sq in rows], dtype=torch.int32, device=dev)
+        ops.gen_select_batch(logits.to(dev), s, cur, 1.2, 2, out=out)
+        return int(out[b]), s[b].cpu(), int(cur[b])
+
+    tok, seq1, cur1 = single()
+    assert tok == want and int(seq1[len(row)]) == want and cur1 == len(row) + 1
+    for got in (batch([row], 0), batch([others[0], row, others[1]], 1)):
+        assert got[0] == tok and torch.equal(got[1], seq1) and got[2] == cur1
+
+
 # ------------------------------------------------------------------------------ GPU: RoPE ----
 
 ROPE_ROWS, ROPE_HH = 50, 288   # hh > 256: the second trip of the copy loop
@@ -807,6 +851,21 @@ def test_gpu_rope_row_copies_the_table_row(pos, dev):
     assert torch.equal(cr[1], cos[pos - 1]) and torch.equal(sr[1], sin[pos - 1])
     assert bool((cr[[0, 2]] == -7.0).all()) and bool((sr[[0, 2]] == -7.0).all())
     assert int(cur) == pos
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("pos", [1, 2, ROPE_ROWS])
+def test_gpu_rope_row_is_rope_rows_row_0(pos, dev):
+    """kd_rope_row == row 0 of kd_rope_rows at nb = 1, at the first two positions and the last table row."""
+    ops = _ops()
+    cos, sin = _rope_tables(dev)
+    cur = torch.tensor([pos], dtype=torch.int32, device=dev)
+    one = torch.full((2, ROPE_HH), -7.0, device=dev)
+    rows = torch.full((2, 1, ROPE_HH), -7.0, device=dev)
+    ops.rope_row(cos, sin, cur, one[0], one[1])
+    ops.rope_rows(cos, sin, cur, rows[0], rows[1])
+    assert torch.equal(one[0], rows[0, 0]) and torch.equal(one[1], rows[1, 0])
+    assert torch.equal(one[0], cos[pos - 1])
 
 
 @pytest.mark.gpu

@@ -17,7 +17,8 @@ PKG = "knowledge_distillation_for_sensory_substitution_in_multimodal_models_amd"
 
 GEMV_SHAPES = [(1152, 896, "bias"), (896, 4864, "residual"), (4864, 896, "swiglu"),
                (21, 40, "none")]   # 4864 as K: the K split; (21, 40): an N tail and a K tail
-ROWS = (1, 17, 40)   # one slab, one row past a slab, two and a half slabs
+ROWS = (1, 17, 40, 81)   # one slab, one row past a slab, two and a half slabs; six slabs over the four slab
+                         # groups of a weight tile: groups 0 and 1 run their slab loop twice, the last slab has one row
 
 
 # ----------------------------------------------------------------------------- CPU ----
@@ -88,7 +89,7 @@ def test_generate_grouped_refuses_bad_groups_before_any_device_work():
 
 @functools.lru_cache(maxsize=2)
 def _gemv_case(N, K, epi):
-    """40 rows of inputs (test_gpu_gemv_batch_matches_torch's distribution) and their fp32 reference."""
+    """max(ROWS) rows of inputs (test_gpu_gemv_batch_matches_torch's distribution) and their fp32 reference."""
     g = torch.Generator(device="cpu").manual_seed(N + K)
     wrows = 2 * N if epi == "swiglu" else N
     w = (torch.randn(wrows, K + 8, generator=g) * 0.05).bfloat16()[:, :K]   # row stride K + 8 (span views)
@@ -153,6 +154,25 @@ def test_gpu_gemv_rows_fused_rmsnorm_is_gemv_batch_row_by_row(rows, N, K, epi, d
     w, x, e, nw, _ = _gemv_case(N, K, epi)
     x = (x.float() * torch.linspace(0.5, 3.0, x.shape[0], device=x.device)[:, None]).bfloat16()   # every row its own rms
     _check_rows_against_batch(ops, w, x, e, N, epi, rows, norm_w=nw, eps=1e-6)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("epi", ["residual", "bias"])
+@pytest.mark.parametrize("rows", [17, 33])
+def test_gpu_gemv_rows_one_tile_per_wave_plan_is_gemv_batch_slab_by_slab(rows, epi, dev):
+    """N = 32776 > 32752 gives the lm_head's plan (one weight tile per wave, K not split), which
+    kd_gemv_rows serves with one kd_gemv_batch pass per slab: the launcher's per-slab offsets of x, y
+    and the residual (the bias must not move).  The N tail is 8 columns; K = 64 keeps the weight at 4 MB."""
+    from importlib import import_module
+    ops = import_module(f"{PKG}.ops")
+    N, K = 32776, 64
+    g = torch.Generator(device="cpu").manual_seed(N + K)
+    w = (torch.randn(N, K, generator=g) * 0.05).bfloat16()
+    x = torch.randn(33, K, generator=g).bfloat16()
+    e = torch.randn(33, N, generator=g).bfloat16()
+    got = _check_rows_against_batch(ops, w.to(dev), x.to(dev), e.to(dev), N, epi, rows)
+    ref = x[:rows].float() @ w.float().t() + (e[:rows] if epi == "residual" else e[0]).float()
+    torch.testing.assert_close(got.float().cpu(), ref, rtol=1e-2, atol=1e-2)
 
 
 QUESTIONS = [(1, 1), (63, 2), (64, 17), (60, 10), (200, 40), (65, 1)]   # (base, S): both sides of the 64-key
