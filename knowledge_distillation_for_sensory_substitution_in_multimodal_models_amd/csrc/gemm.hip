@@ -219,6 +219,9 @@ inline int pick_gm(int tiles_m, int tiles_n) {
 
 // Block -> tile map: XCD-aware bijective remap (the blocks dispatched to one XCD, b, b+8,
 // ..., get consecutive ids), offset by the launch's first tile, then the grouped order.
+// The remap expression stands three times (here and twice in k_gemm8: the stream-K runs, the fold's
+// tickets): behind one __device__ helper the v8 kernels compiled to a different register allocation
+// and schedule (658 differing lines of ISA), so the copies stay.
 __device__ __forceinline__ void tile_of_b(int b, int nwg, int tiles_m, int tiles_n, int& tm, int& tn, int tile0 = 0,
                                           int gm = 0) {
     const int q8 = nwg / 8, r8 = nwg % 8, x = b % 8;
@@ -1137,14 +1140,42 @@ __device__ __forceinline__ uint32_t voff8(int i, int lane, int64_t ld, int r0, i
     }
 }
 
-// EXP: bit 2 = the fused SwiGLU build (KD_ACT_SWIGLU: gathered gate|up B rows, GLU epilogue;
-// its own kernel, so its launches are exactly the gate|up GEMMs in a kernel trace; the
-// production non-GLU build carries no GLU code). Diagnostic variants 17-19 only: bit 0 writes per-wave s_memtime
-// cycle totals (step-end sync, MFMA units, prologue, epilogue) as uint32 to p.aux (which
-// then carries no pre-activation output); bit 1 drops the in-loop DMA (timing ablation:
-// WRONG results); bit 6 re-reads stage 0 for every stage (same addresses, L2-hot:
-// separates issue cost from memory-system cost; WRONG results).
-// Bit 3 (K-major x K-major only): REGISTER staging instead of LDS-DMA. A k-step's 64
+// The builds of the 256 x 256 v8 tile kernel (k_gemm8's EXP argument, OR-ed; k_gemm8f8 and the A/B
+// library's v11 / v12 take the same names for the builds they have).  Every flag is a build of its
+// own, so the plain kernel (EXP = 0) carries none of the other builds' code and each build's launches
+// are their own line in a kernel trace.  The variants are kd_gemm_desc.variant codes (VARIANTS below).
+enum : int {
+    // diagnostic, A/B library only: per-wave s_memtime cycle totals (step-end sync, MFMA units,
+    // prologue, epilogue) as uint32 to p.aux, which then carries no pre-activation output (variant 17;
+    // with G8_SWIGLU, variant 28, to the workspace p.sk_ws: that build keeps its aux)
+    G8_STAMP = 1,
+    // diagnostic (variant 18): drops the in-loop DMA (timing ablation: WRONG results)
+    G8_NODMA = 2,
+    // the fused SwiGLU build (KD_ACT_SWIGLU: gathered gate|up B rows, GLU epilogue), K-major B only
+    G8_SWIGLU = 4,
+    // register staging instead of LDS-DMA, K-major x K-major only (variant 22: a negative result, below)
+    G8_REGSTAGE = 8,
+    // the epilogue also writes the tile's row statistics (kd_gemm_desc.row_stats, the lm_head GEMMs
+    // of the KD step), K-major x K-major only
+    G8_ROWSTATS = 32,
+    // diagnostic (variant 19): re-reads stage 0 for every stage (same addresses, L2-hot: separates
+    // issue cost from memory-system cost; WRONG results)
+    G8_HOT = 64,
+    // B PRE-TILED (kd_gemm_desc.b_pretiled, kd_gemm_pretile): the K-major B operand is stored as each
+    // 256-row tile's stages, [tile][stage][256 rows][64 B] with the LDS chunk swizzle (and, for the
+    // SwiGLU build, the gate|up row gather) already applied, zero-padded past N and K, so every DMA
+    // instruction reads ONE contiguous KiB (8 whole cache lines) instead of 16 half-lines, and lands
+    // the same LDS image (bit-identical results)
+    G8_PRETILED = 256,
+    // the SwiGLU build with the round-4 (unpacked) epilogue (KD_GLU_EPI_V0=1; A/B library only)
+    G8_GLU_V0 = 512,
+    // stream-K (variant 21): whole waves data-parallel, the rest in runs folded in-launch (GemmP.sk_*)
+    G8_STREAMK = 1024,
+    // split-K with the in-launch fold (variant 32): no partial planes, no reduce launch
+    G8_FOLD = 2048,
+};
+#define KD_SB __builtin_amdgcn_sched_barrier(0);   // the k-step macros of v8, the fp8 kernel, v8n, v11 and v12
+// G8_REGSTAGE: REGISTER staging instead of LDS-DMA. A k-step's 64
 // MFMAs (16x16x32, each holding the SIMD's vector issue for 8 of its 16 cycles) leave 512
 // issue cycles for everything else, and its 8 LDS-DMA pieces cost ~60 each (more beside
 // 16 fragment reads: MI355X_MICROARCH constants table) — the measured step is 1243 cycles,
@@ -1238,24 +1269,16 @@ __device__ __forceinline__ bool sk_fold_tile(const SkFold& f, f32x4 (&acc)[8][8]
 
 template <bool A_MN, bool B_MN, int EXP>
 __device__ __forceinline__ void g8_tile(GemmP p, int tm, int tn, char* smem, const SkFold* fold = nullptr) {
-    constexpr bool STAMP = EXP & 1, NODMA = EXP & 2, HOT = EXP & 64;
-    constexpr bool RS = (EXP & 8) && !A_MN && !B_MN;
-    // bit 5: the epilogue also writes the tile's row statistics (kd_gemm_desc.row_stats, the
-    // lm_head GEMMs of the KD step): a build of its own, so the plain forward kernel carries none
-    // of that code and the lm_head launches are their own line in a kernel trace
-    constexpr bool RSTATS = (EXP & 32) && !A_MN && !B_MN;
-    // bit 8: B PRE-TILED (kd_gemm_desc.b_pretiled, kd_gemm_pretile): the K-major B operand is stored
-    // as each 256-row tile's stages, [tile][stage][256 rows][64 B] with the LDS chunk swizzle (and, for
-    // the SwiGLU build, the gate|up row gather) already applied, zero-padded past N and K, so every
-    // DMA instruction reads ONE contiguous KiB (8 whole cache lines) instead of 16 half-lines, and
-    // lands the same LDS image (bit-identical results)
-    constexpr bool TB = (EXP & 256) && !B_MN && !RS;
+    constexpr bool STAMP = EXP & G8_STAMP, NODMA = EXP & G8_NODMA, HOT = EXP & G8_HOT;
+    constexpr bool RS = (EXP & G8_REGSTAGE) && !A_MN && !B_MN;
+    constexpr bool RSTATS = (EXP & G8_ROWSTATS) && !A_MN && !B_MN;
+    constexpr bool TB = (EXP & G8_PRETILED) && !B_MN && !RS;
     const int nkt = (p.K + BK2 - 1) / BK2;   // stages per pre-tiled tile
 
     uint32_t* stamps = nullptr;
     // the SwiGLU stamp build (variant 28) keeps its aux output: stamps go to the workspace (p.sk_ws)
     if (STAMP) {
-        if ((EXP & 4) && !B_MN) stamps = (uint32_t*)p.sk_ws;
+        if ((EXP & G8_SWIGLU) && !B_MN) stamps = (uint32_t*)p.sk_ws;
         else { stamps = (uint32_t*)p.aux; p.aux = nullptr; }
     }
     uint64_t mk[2] = {0, 0};
@@ -1282,7 +1305,7 @@ __device__ __forceinline__ void g8_tile(GemmP p, int tm, int tn, char* smem, con
     }
     auto kst = [&](int st) { return (rot == 0 || st >= nk) ? st : (st + rot >= nk ? st + rot - nk : st + rot); };
     const __amdgpu_buffer_rsrc_t rsAk = make_rsrc(p.A + (A_MN ? 0 : (int64_t)m0 * p.lda), A_MN ? 0u : rec_bytes(min(256, p.M - m0), p.lda));
-    constexpr bool glu = !B_MN && (EXP & 4);   // gate rows [nb, nb+128) and up rows [I+nb, I+nb+128)
+    constexpr bool glu = !B_MN && (EXP & G8_SWIGLU);   // gate rows [nb, nb+128) and up rows [I+nb, I+nb+128)
     const int nb = tn * 128;
     const __amdgpu_buffer_rsrc_t rsBk =
         TB ? make_rsrc(p.B + (int64_t)tn * nkt * (256 * BK2), (uint32_t)nkt * (256 * BK2 * 2))
@@ -1417,7 +1440,6 @@ __device__ __forceinline__ void g8_tile(GemmP p, int tm, int tn, char* smem, con
     }
     KD_G8_SYNC()
     __builtin_amdgcn_sched_barrier(0);
-#define KD_SB __builtin_amdgcn_sched_barrier(0);
 #define KD_G8_STEP(SL, CA, CB, NA, NB, FT)                                                                   \
     {                                                                                                         \
         const int t_ = t + (SL);                                                                              \
@@ -1464,7 +1486,6 @@ __device__ __forceinline__ void g8_tile(GemmP p, int tm, int tn, char* smem, con
     if (rem > 2) KD_G8_STEP(2, xa, xb, ya, yb, PartT)
 #undef KD_G8_STEP
 #undef KD_G8_SYNC
-#undef KD_SB
     // drain the ring (out-of-range DMAs still write LDS) and the MFMA pipe before the
     // accumulators are read back (asm MFMAs are invisible to the hazard recognizer)
     asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)\n\ts_nop 15\n\ts_nop 15" ::: "memory");
@@ -1472,11 +1493,11 @@ __device__ __forceinline__ void g8_tile(GemmP p, int tm, int tn, char* smem, con
     uint64_t te0 = 0;
     if (STAMP) { te0 = __builtin_amdgcn_s_memtime(); s_units += te0 - tprev; }
     __syncthreads();
-    if constexpr ((EXP & (1024 | 2048)) != 0) {   // stream-K / split-K fold builds: a published piece ends here
+    if constexpr ((EXP & (G8_STREAMK | G8_FOLD)) != 0) {   // stream-K / split-K fold builds: a published piece ends here
         if (fold != nullptr && !sk_fold_tile(*fold, acc, tid, lane, wid, smem)) return;
     }
 #ifdef KD_AB_BUILD
-    if constexpr (!A_MN && !B_MN && (EXP & 512)) epilogue_glu_v0<128, 128, 8, 8, NTH8>(p, acc, smem, m0, nb, wm, wn, lane, tid);
+    if constexpr (!A_MN && !B_MN && (EXP & G8_GLU_V0)) epilogue_glu_v0<128, 128, 8, 8, NTH8>(p, acc, smem, m0, nb, wm, wn, lane, tid);
     else
 #endif
     if (!A_MN && !B_MN && glu) epilogue_glu<128, 128, 8, 8, NTH8, false, STAMP>(p, acc, smem, m0, nb, wm, wn, lane, tid, mk);
@@ -1516,7 +1537,7 @@ template <bool A_MN, bool B_MN, int EXP = 0>
 __global__ void __launch_bounds__(NTH8, 1) k_gemm8(GemmP p_) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     const int tiles_m = (p_.M + 255) / 256, tiles_n = (p_.N + 255) / 256;
-    if constexpr ((EXP & 1024) != 0) {   // the stream-K build (variant 21): data-parallel whole waves, then runs
+    if constexpr ((EXP & G8_STREAMK) != 0) {   // the stream-K build (variant 21): data-parallel whole waves, then runs
         const int nkt = p_.sk_steps, G = p_.sk_grid;
         const bool dp = (int)blockIdx.x < p_.sk_dp;
         // run w of workgroup i (sk_dp % 8 == 0, so workgroup i sits on XCD i % 8): the runs of one XCD
@@ -1557,7 +1578,7 @@ __global__ void __launch_bounds__(NTH8, 1) k_gemm8(GemmP p_) {
         }
         return;
     }
-    if constexpr ((EXP & 2048) != 0) {   // split-K with the in-launch fold (variant 32): no partial planes,
+    if constexpr ((EXP & G8_FOLD) != 0) {   // split-K with the in-launch fold (variant 32): no partial planes,
         // no reduce launch -- split blockIdx.y publishes its accumulators, the tile's last arriver sums the
         // S pieces in split order and runs the full epilogue
         GemmP q = p_;
@@ -1596,7 +1617,7 @@ __global__ void __launch_bounds__(NTH8, 1) k_gemm8(GemmP p_) {
 // member i's tiles in that member's own order: the XCD remap runs on the member-local index (the
 // workgroups b, b + 8, ... of one XCD still get consecutive tiles; only which XCD takes which
 // chunk is rotated by t0[i] % 8), with the member's gm / stagger, so every tile runs exactly the
-// g8_tile call of the member's single unsplit k_gemm8<true, true, 0> launch: the same bits.
+// g8_tile call of the member's single unsplit plain k_gemm8<true, true> launch: the same bits.
 constexpr int GROUP_MAX = 4;
 struct GemmGroupP {
     GemmP p[GROUP_MAX];
@@ -1700,7 +1721,7 @@ __device__ __forceinline__ void f8_to_lds(const f32x16 (&acc)[4][4], char* smem,
 // after the last (asm, hazard-invisible) MFMA, before its results had landed.
 template <int EXP, int ACT>
 __global__ void __launch_bounds__(NTH8, 1) k_gemm8f8(GemmP p) {
-    constexpr bool glu = EXP & 4;
+    constexpr bool glu = EXP & G8_SWIGLU;
     constexpr int SA = 256 * 64, SS = 2 * SA;   // 16 KiB per operand stage, 32 KiB per slot
     extern __shared__ __attribute__((aligned(16))) char smem[];
     const int tid = threadIdx.x, lane = tid & 63;
@@ -1774,7 +1795,6 @@ __global__ void __launch_bounds__(NTH8, 1) k_gemm8f8(GemmP p) {
     }
     KD_F8_SYNC()
     __builtin_amdgcn_sched_barrier(0);
-#define KD_SB __builtin_amdgcn_sched_barrier(0);
 #define KD_F8_STEP(SL, CA, CB, NA, NB, FT)                                                         \
     {                                                                                               \
         const int t_ = t + (SL);                                                                    \
@@ -1812,7 +1832,6 @@ __global__ void __launch_bounds__(NTH8, 1) k_gemm8f8(GemmP p) {
     if (rem > 2) KD_F8_STEP(2, xa, xb, ya, yb, PartT)
 #undef KD_F8_STEP
 #undef KD_F8_SYNC
-#undef KD_SB
     asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)\n\ts_nop 15\n\ts_nop 15" ::: "memory");
     __builtin_amdgcn_sched_barrier(0);
     __syncthreads();
@@ -2033,6 +2052,53 @@ bool glu_epi_v0() {
 }
 #endif
 
+// kd_gemm_desc.variant, in one table: what each code runs, whether the product library accepts it
+// (ab: the tools' A/B library only -- KD_AB_BUILD, python csrc/build.py --ab -- the negative-result
+// and diagnostic builds of DESIGN §3), the plan candidate it forces (plan_gemm's index: 0 / 1 / 2
+// the v3 tiles, 3 v8, 4 v9; -1: the cost model chooses) and the v8 build it runs (G8_* flags).
+// variant_known, plan_gemm and launch_gemm all read it.
+struct VariantInfo { int code; const char* what; bool ab; int cand; int flags; };
+constexpr VariantInfo VARIANTS[] = {
+    {0, "the cost model's choice", false, -1, 0},
+    {1, "v1 128x128", false, -1, 0},
+    {2, "v3 256x256", false, 0, 0}, {3, "v3 256x128", false, 1, 0}, {4, "v3 128x256", false, 2, 0},
+    {5, "v3 256x256", false, 0, 0}, {6, "v3 256x128", false, 1, 0}, {7, "v3 128x256", false, 2, 0},
+    {16, "v8 256x256 (4 waves, AGPR accumulators)", false, 3, 0},
+    {17, "v8 stamps, every layout", true, 3, G8_STAMP},
+    {18, "v8 without the in-loop DMA (K-major x K-major)", true, 3, G8_NODMA},
+    {19, "v8 re-reading stage 0 (K-major x K-major)", true, 3, G8_HOT},
+    {20, "v9 (eight-wave ping-pong)", true, 4, 0},
+    {21, "stream-K on v8 where its workspace fits, else v8", false, 3, G8_STREAMK},
+    {22, "v8 register-staged (K-major x K-major; negative result)", true, 3, G8_REGSTAGE},
+    {23, "v11 (32x32x16 MFMAs) on v8's K-major tiles", true, 3, 0},
+    {24, "v8 (= 16, also where KD_GEMM_V11 / KD_GEMM_V12 is set)", false, 3, 0},
+    {26, "v12 (whole-line staging) on v8's K-major tiles", true, 3, 0},
+    {27, "v12 without the odd-step barriers", true, 3, 0},
+    {28, "the v8 SwiGLU build with stamps", true, 3, G8_SWIGLU | G8_STAMP},
+    {30, "v8n (256x128, two workgroups per CU), unsplit", true, 3, 0},
+    {32, "v8, split tiles folded in-launch", false, 3, G8_FOLD},
+};
+const VariantInfo* variant_info(int v) {
+    for (const VariantInfo& i : VARIANTS)
+        if (i.code == v) return &i;
+    return nullptr;
+}
+bool variant_known(int v) {
+    const VariantInfo* i = variant_info(v);
+#ifdef KD_AB_BUILD
+    return i != nullptr;
+#else
+    return i && !i->ab;
+#endif
+}
+
+// stream-K over `tiles` 256 x 256 tiles: enough k-steps past the data-parallel prefix, and the
+// workspace holds the tickets and the partial-tile slots
+bool sk_fits(int64_t tiles, int64_t nk, const kd_gemm_desc* d) {
+    const int64_t dp = sk_dp_tiles(tiles, nk);
+    return (tiles - dp) * nk >= 2 * SK_GRID && d->workspace && d->workspace_bytes >= sk_workspace_bytes(tiles - dp);
+}
+
 GemmPlan plan_gemm(const kd_gemm_desc* d, uint64_t ws_cap) {
     const int64_t M = d->M, N = d->N;
     const int64_t t256 = (int64_t)ceil_div(d->M, 256) * ceil_div(d->N, 256);
@@ -2067,8 +2133,8 @@ GemmPlan plan_gemm(const kd_gemm_desc* d, uint64_t ws_cap) {
     const double* fixed = fixed_c[kk ? 0 : 1];
     const int vcode[5] = {2, 3, 4, 16, 20};
     const int64_t nk = ceil_div(d->K, BK2);
-    // forced: variants 2/5 v3 256x256, 3/6 256x128, 4/7 128x256, 16+ v8; 0 = model's choice
-    const int fv = d->variant == 20 ? 4 : (d->variant >= 16 ? 3 : (d->variant >= 5 ? d->variant - 5 : (d->variant >= 2 ? d->variant - 2 : -1)));
+    const VariantInfo* vi = variant_info(d->variant);
+    const int fv = vi ? vi->cand : -1;   // the forced candidate (VARIANTS); -1 = the model's choice
     const double out_e = (double)((d->c_dtype == KD_DTYPE_F32 ? 4 : 2) * (d->accumulate ? 2 : 1) +
                                   (d->residual ? (d->residual_dtype == KD_DTYPE_F32 ? 4 : 2) : 0) +
                                   (d->aux ? 2 : 0));   // epilogue bytes per element
@@ -2119,6 +2185,70 @@ GemmPlan plan_gemm(const kd_gemm_desc* d, uint64_t ws_cap) {
     return best;
 }
 
+// the shapes and alignments the tiled kernels (v3 / v8) take; every other GEMM runs on v1
+bool c_rows_ok16(const kd_gemm_desc* d) {   // 16-B aligned C and residual rows
+    return (d->qkv || ((d->ldc % 8 == 0) && ((uintptr_t)d->C % 16 == 0))) &&
+           (!d->residual || ((d->ldr % 8 == 0) && ((uintptr_t)d->residual % 16 == 0)));
+}
+bool tiled_ok(const kd_gemm_desc* d) {
+    const bool amn = d->a_layout == KD_LAYOUT_MN_MAJOR, bmn = d->b_layout == KD_LAYOUT_MN_MAJOR;
+    return d->N % 8 == 0 && c_rows_ok16(d) && d->M >= 128 && d->N >= 128 &&
+           ((uint64_t)d->M * d->N >= (1ull << 20) || (d->workspace && d->K >= 2048 && d->split_k != 1)) &&
+           (!amn || d->M % 8 == 0) && (!bmn || d->N % 8 == 0) &&
+           (uint64_t)BK2 * (amn ? d->lda : 0) * 2 < 0x7FFFFFFFull;
+}
+
+// Which launch a descriptor takes, decided in one place: launch_gemm switches on it, kd_gemm_plan
+// reports its plan.  The v8-only routes run every 256 x 256 tile unsplit; V8N is in the A/B library only.
+enum class Route { F8, ROW_STATS, SWIGLU, SWIGLU_PRETILED, SWIGLU_STREAMK, PRETILED, V8N, TILED, V1 };
+struct GemmRoute { Route route; GemmPlan plan; };
+GemmRoute gemm_route(const kd_gemm_desc* d) {
+    const GemmPlan v8{16, 1, d->K, 0};
+    if (d->ab_dtype == KD_DTYPE_FP8_E4M3) return {Route::F8, v8};
+    if (d->row_stats) return {Route::ROW_STATS, v8};
+    if (d->act == KD_ACT_SWIGLU) {
+        if (d->b_pretiled) return {Route::SWIGLU_PRETILED, v8};
+        const bool sk = d->variant == 21 && sk_fits((int64_t)ceil_div(d->M, 256) * (d->N / 256), ceil_div(d->K, BK2), d);
+        return {sk ? Route::SWIGLU_STREAMK : Route::SWIGLU, v8};
+    }
+    if (d->b_pretiled) return {Route::PRETILED, v8};
+#ifdef KD_AB_BUILD
+    if (d->variant == 30) return {Route::V8N, GemmPlan{30, 1, d->K, 0}};
+#endif
+    if (d->variant == 1 || !tiled_ok(d)) return {Route::V1, GemmPlan{1, 1, d->K, 0}};
+    kd_gemm_desc d1 = *d;
+    if (d->act == KD_ACT_DGELU_TANH || d->act == KD_ACT_DSWIGLU || d->qkv)
+        d1.split_k = 1;   // the fused backward activation / q|k|v scatter are never split-K
+    return {Route::TILED, plan_gemm(&d1, d->workspace ? d->workspace_bytes : 0)};
+}
+
+// The kernel parameters every launch path shares; a path then sets only what is its own.  Value-
+// initialised, so a field no path sets is 0 / null = off.
+GemmP make_params(const kd_gemm_desc* d) {
+    GemmP p{};
+    p.A = (const bf16*)d->A; p.B = (const bf16*)d->B; p.C = d->C;
+    p.bias = d->bias; p.resid = (const bf16*)d->residual; p.aux = (bf16*)d->aux; p.alpha_dev = d->alpha_dev;
+    p.lda = d->lda; p.ldb = d->ldb; p.ldc = d->ldc; p.ldr = d->ldr; p.ld_aux = d->ld_aux;
+    p.M = d->M; p.N = d->N; p.K = d->K; p.alpha = d->alpha;
+    p.c_f32 = d->c_dtype == KD_DTYPE_F32; p.accumulate = d->accumulate; p.bias_f32 = d->bias_dtype == KD_DTYPE_F32;
+    p.act = d->act; p.res_mod = d->residual_row_mod;
+    p.res_f32 = d->residual && d->residual_dtype == KD_DTYPE_F32;
+    p.kchunk = d->K; p.gy = 1; p.rst_inv_t = 1.f;
+    return p;
+}
+
+// The layout pair as template arguments, in one place: a kernel family's four layout builds as a
+// table that layout_index(amn, bmn) indexes (k_gemm's and, in the A/B library, k_gemm9's stand where
+// they are launched).
+using GemmKernel = void (*)(GemmP);
+inline int layout_index(bool amn, bool bmn) { return amn ? (bmn ? 2 : 3) : (bmn ? 1 : 0); }
+template <int FLAGS>
+constexpr GemmKernel V8[4] = {k_gemm8<false, false, FLAGS>, k_gemm8<false, true, FLAGS>, k_gemm8<true, true, FLAGS>,
+                              k_gemm8<true, false, FLAGS>};
+template <int TBM, int TBN>
+constexpr GemmKernel V3[4] = {k_gemm3<TBM, TBN, false, false>, k_gemm3<TBM, TBN, false, true>, k_gemm3<TBM, TBN, true, true>,
+                              k_gemm3<TBM, TBN, true, false>};
+
 }  // namespace
 
 
@@ -2141,15 +2271,8 @@ int launch_gemm_f8(const kd_gemm_desc* d, void* stream_) {
     KD_CHECK_SHAPE(d->ldc >= (d->act == KD_ACT_SWIGLU ? d->N / 2 : d->N), "gemm fp8: ldc < N (N/2 for swiglu)");
     KD_CHECK_SHAPE(!d->residual || d->ldr >= d->N, "gemm fp8: ldr < N");
     KD_CHECK_SHAPE(!d->aux || d->ld_aux >= d->N, "gemm fp8: ld_aux < N");
-    GemmP p;
-    std::memset(&p, 0, sizeof(p));
-    p.A = (const bf16*)d->A; p.B = (const bf16*)d->B; p.C = d->C;
-    p.bias = d->bias; p.resid = (const bf16*)d->residual; p.aux = (bf16*)d->aux; p.alpha_dev = d->alpha_dev;
-    p.lda = d->lda; p.ldb = d->ldb; p.ldc = d->ldc; p.ldr = d->ldr; p.ld_aux = d->ld_aux;
-    p.M = d->M; p.N = d->N; p.K = d->K; p.alpha = d->alpha;
-    p.c_f32 = 0; p.accumulate = d->accumulate; p.bias_f32 = d->bias_dtype == KD_DTYPE_F32;
-    p.act = d->act; p.res_mod = d->residual_row_mod;
-    p.kchunk = d->K; p.sa = d->a_scale; p.sb = d->b_scale;
+    GemmP p = make_params(d);   // bf16 C and residual (checked above); no k-loop stagger in this kernel
+    p.sa = d->a_scale; p.sb = d->b_scale;
     hipStream_t st = as_stream(stream_);
     if (d->act == KD_ACT_SWIGLU) {
         KD_CHECK_SHAPE(d->N % 256 == 0, "gemm fp8 swiglu: N = 2I needs I % 128 == 0");
@@ -2157,7 +2280,7 @@ int launch_gemm_f8(const kd_gemm_desc* d, void* stream_) {
         p.glu = d->N / 2; p.act = KD_ACT_NONE;
         p.gx = ceil_div(d->M, 256) * (d->N / 256); p.gy = 1;
         p.gm = pick_gm(ceil_div(d->M, 256), d->N / 256);
-        hipLaunchKernelGGL((k_gemm8f8<4, KD_ACT_NONE>), dim3(p.gx), dim3(NTH8), F8_LDS, st, p);
+        hipLaunchKernelGGL((k_gemm8f8<G8_SWIGLU, KD_ACT_NONE>), dim3(p.gx), dim3(NTH8), F8_LDS, st, p);
         KD_LAUNCH_CHECK("k_gemm8f8<swiglu>");
         return KD_OK;
     }
@@ -2230,31 +2353,23 @@ int launch_gemm_pretile(const void* W, int64_t ldw, int N, int K, int glu, void*
 }
 
 #ifdef KD_AB_BUILD
-// v11 (32x32x16 MFMAs) in place of v8 for K-major x K-major tiles: forced variant 23, or
-// KD_GEMM_V11=1 wherever v8 would run (opt-in; 24 forces v8 for A/B)
-static bool use_v11(int variant) {
-    if (variant == 23) return true;
+// v11 (32x32x16 MFMAs; forced variant 23, KD_GEMM_V11=1) or v12 (whole-line staging of K-major
+// operands, bit-identical to v8; forced variant 26, KD_GEMM_V12=1) in place of v8 for K-major x
+// K-major tiles: the forced variant, or the environment switch wherever v8 would run (opt-in; 24
+// forces v8 for A/B).  v12 measured faster than v8 only with the weights warm in the Infinity Cache
+// (back-to-back calls, profiles/r04/ab_v12_vs_v8.txt); in the step's cache state -- every weight
+// read cold, a whole step after its last use -- slower than v8 on every shape
+// (profiles/r04/ab_cold.txt): its stage pairs halve the prefetch depth.
+static bool use_alt(int variant, int forced, const char* env) {
+    if (variant == forced) return true;
     if (variant != 0 && variant != 16) return false;
-    static const int env = [] { const char* e = std::getenv("KD_GEMM_V11"); return e ? std::atoi(e) : -1; }();
-    return env == 1;
+    const char* e = std::getenv(env);
+    return e && std::atoi(e) == 1;
 }
-
-// v12 (whole-line staging of K-major operands, bit-identical to v8): forced variant 26, or
-// KD_GEMM_V12=1 wherever v8 would run (opt-in; 24 forces v8).  Measured faster than v8 only with
-// the weights warm in the Infinity Cache (back-to-back calls, profiles/r04/ab_v12_vs_v8.txt); in
-// the step's cache state -- every weight read cold, a whole step after its last use -- slower than
-// v8 on every shape (profiles/r04/ab_cold.txt): its stage pairs halve the prefetch depth.
-static bool use_v12(int variant) {
-    if (variant == 26) return true;
-    if (variant != 0 && variant != 16) return false;
-    static const int env = [] { const char* e = std::getenv("KD_GEMM_V12"); return e ? std::atoi(e) : -1; }();
-    return env == 1;
-}
+static bool use_v11(int variant) { return use_alt(variant, 23, "KD_GEMM_V11"); }
+static bool use_v12(int variant) { return use_alt(variant, 26, "KD_GEMM_V12"); }
 #endif
 
-// the variants kd_gemm accepts: 0 auto, 1 v1, 2-7 v3 tiles, 16 v8, 21 stream-K, 24 (= 16); the
-// tools' A/B library (KD_AB_BUILD: python csrc/build.py --ab) also the negative-result and
-// diagnostic builds 17-20, 22, 23, 26-28
 // workgroups of a split-K / stream-K fold launch over `items` (tile, row slab) items: one each, or
 // at most KD_SK_REDUCE_GRID (A/B: the fold runs beside the other stream's GEMMs)
 static unsigned reduce_grid(int items) {
@@ -2262,20 +2377,8 @@ static unsigned reduce_grid(int items) {
     return (unsigned)(cap > 0 && cap < items ? cap : items);
 }
 
-static bool variant_known(int v) {
-    if ((v >= 0 && v <= 7) || v == 16 || v == 21 || v == 24 || v == 32) return true;
-#ifdef KD_AB_BUILD
-    if ((v >= 17 && v <= 20) || v == 22 || v == 23 || (v >= 26 && v <= 28) || v == 30) return true;
-#endif
-    return false;
-}
-
 // stream-K launch setup over `tiles` 256 x 256 tiles: the data-parallel prefix, the run grid, the
 // tickets (zeroed by a memset node ahead of every launch: Guideline 16) and the partial-tile slots
-static bool sk_fits(int64_t tiles, int64_t nk, const kd_gemm_desc* d) {
-    const int64_t dp = sk_dp_tiles(tiles, nk);
-    return (tiles - dp) * nk >= 2 * SK_GRID && d->workspace && d->workspace_bytes >= sk_workspace_bytes(tiles - dp);
-}
 static int sk_setup(GemmP& q, int64_t tiles, const kd_gemm_desc* d, hipStream_t st) {
     const int64_t dp = sk_dp_tiles(tiles, ceil_div(d->K, BK2));
     KD_CHECK_ARG(d->workspace && d->workspace_bytes >= sk_workspace_bytes(tiles - dp), "gemm: stream-K workspace too small");
@@ -2287,6 +2390,10 @@ static int sk_setup(GemmP& q, int64_t tiles, const kd_gemm_desc* d, hipStream_t 
         return fail(KD_ERR_LAUNCH, "gemm: stream-K ticket memset");
     return KD_OK;
 }
+
+// the two routes that are not one v8 launch, below launch_gemm (the kernel builds keep their order in the object)
+static int launch_tiled(const kd_gemm_desc* d, const GemmPlan& pl, GemmP& p, hipStream_t st);
+static int launch_v1(const kd_gemm_desc* d, GemmP& p, hipStream_t st);
 
 int launch_gemm(const kd_gemm_desc* d, void* stream_) {
     KD_CHECK_ARG(d != nullptr, "gemm: null descriptor");
@@ -2301,7 +2408,8 @@ int launch_gemm(const kd_gemm_desc* d, void* stream_) {
                                     d->b_layout == KD_LAYOUT_K_MAJOR && !d->row_stats && d->split_k <= 1 &&
                                     (d->variant == 0 || d->variant == 16 || d->variant == 24)),
                  "gemm b_pretiled: K-major bf16 operands on the 256x256 v8 kernel, no split-K / row_stats");
-    if (d->ab_dtype == KD_DTYPE_FP8_E4M3) return launch_gemm_f8(d, stream_);
+    const GemmRoute rt = gemm_route(d);
+    if (rt.route == Route::F8) return launch_gemm_f8(d, stream_);
     KD_CHECK_ARG(d->act >= KD_ACT_NONE && d->act <= KD_ACT_DSWIGLU, "gemm: act");
     const bool dact = d->act == KD_ACT_DGELU_TANH || d->act == KD_ACT_DSWIGLU;
     KD_CHECK_ARG(d->act == KD_ACT_NONE || dact || (d->a_layout == KD_LAYOUT_K_MAJOR && d->b_layout == KD_LAYOUT_K_MAJOR &&
@@ -2347,17 +2455,8 @@ int launch_gemm(const kd_gemm_desc* d, void* stream_) {
         if (bl && blas_eligible(d) && (bl == 1 || blas_wins(d))) return blas_gemm(d, as_stream(stream_));
     }
 #endif
-    GemmP p;
-    p.A = (const bf16*)d->A; p.B = (const bf16*)d->B; p.C = d->C;
-    p.bias = d->bias; p.resid = (const bf16*)d->residual; p.aux = (bf16*)d->aux; p.alpha_dev = d->alpha_dev;
-    p.lda = d->lda; p.ldb = d->ldb; p.ldc = d->ldc; p.ldr = d->ldr; p.ld_aux = d->ld_aux;
-    p.M = d->M; p.N = d->N; p.K = d->K; p.alpha = d->alpha;
-    p.c_f32 = d->c_dtype == KD_DTYPE_F32; p.accumulate = d->accumulate; p.bias_f32 = d->bias_dtype == KD_DTYPE_F32;
-    p.act = d->act;
-    p.res_mod = d->residual_row_mod;
-    p.res_f32 = d->residual && d->residual_dtype == KD_DTYPE_F32;
-    p.sq = p.sk = p.sv = nullptr; p.rcos = p.rsin = nullptr;
-    p.sS = p.snq = p.snkv = p.shd = p.shdp = 0;
+    GemmP p = make_params(d);
+    p.stagger = ab_knob("KD_GEMM_STAGGER", 1);
     if (d->qkv) {
         const kd_qkv_scatter& q = *d->qkv;
         const bool rope = q.cos_t != nullptr;
@@ -2374,31 +2473,21 @@ int launch_gemm(const kd_gemm_desc* d, void* stream_) {
         p.sq = (bf16*)q.q; p.sk = (bf16*)q.k; p.sv = (bf16*)q.v; p.rcos = q.cos_t; p.rsin = q.sin_t;
         p.sS = q.S; p.snq = q.nq; p.snkv = q.nkv; p.shd = q.hd; p.shdp = q.hdp;
     }
-    p.kchunk = d->K; p.split_stride = 0; p.glu = 0; p.tile0 = 0;
-    p.sa = p.sb = nullptr; p.gx = 0; p.gy = 1;
-    p.sk_steps = 0; p.sk_grid = 0; p.sk_ws = nullptr; p.sk_dp = 0; p.sk_cnt = nullptr;
-    p.gm = 0;
-    p.rst = nullptr; p.rst_nt = p.rst_vs = p.rst_top2 = 0; p.rst_inv_t = 1.f;
-    p.stagger = ab_knob("KD_GEMM_STAGGER", 1);
-    p.stag_g = 0;
     hipStream_t st = as_stream(stream_);
     const bool amn = d->a_layout == KD_LAYOUT_MN_MAJOR, bmn = d->b_layout == KD_LAYOUT_MN_MAJOR;
-    const bool c_ok16 = (d->qkv || ((d->ldc % 8 == 0) && ((uintptr_t)d->C % 16 == 0))) &&
-                        (!d->residual || ((d->ldr % 8 == 0) && ((uintptr_t)d->residual % 16 == 0)));
-    const bool big_ok = d->N % 8 == 0 && c_ok16 && d->M >= 128 && d->N >= 128 &&
-                        ((uint64_t)d->M * d->N >= (1ull << 20) || (d->workspace && d->K >= 2048 && d->split_k != 1)) &&
-                        (!amn || d->M % 8 == 0) && (!bmn || d->N % 8 == 0) &&
-                        (uint64_t)BK2 * (amn ? d->lda : 0) * 2 < 0x7FFFFFFFull;
+    const bool c_ok16 = c_rows_ok16(d), big_ok = tiled_ok(d);
     KD_CHECK_ARG(!dact || big_ok, "gemm backward activation: needs the tiled kernels (M, N >= 128, M*N >= 2^20)");
     KD_CHECK_ARG(!d->qkv || (big_ok && d->variant != 1),
                  "gemm qkv: needs the tiled kernels (M, N >= 128, M*N >= 2^20)");
-    kd_gemm_desc d1;
-    if ((dact || d->qkv) && d->split_k != 1) {   // the fused backward activation / q|k|v scatter are never split-K
-        d1 = *d;
-        d1.split_k = 1;
-        d = &d1;
-    }
-    if (d->row_stats) {   // the lm_head GEMM with the KD loss's row statistics, on v8 (no split)
+    // the v8-only routes: every 256 x 256 tile (SwiGLU: 128 gate + 128 up columns), unsplit
+    const int tiles_m8 = ceil_div(d->M, 256), tiles_n8 = d->act == KD_ACT_SWIGLU ? d->N / 256 : ceil_div(d->N, 256);
+    const dim3 grid8(tiles_m8 * tiles_n8);
+    const size_t lds8 = gemm2_lds<256, 256>();
+    p.gm = pick_gm(tiles_m8, tiles_n8);
+    p.gx = (int)grid8.x;
+    switch (rt.route) {
+    case Route::F8: break;   // left above
+    case Route::ROW_STATS:   // the lm_head GEMM with the KD loss's row statistics
         KD_CHECK_ARG(!amn && !bmn && d->c_dtype == KD_DTYPE_BF16 && !d->bias && d->act == KD_ACT_NONE && !d->residual &&
                          !d->aux && !d->accumulate && !d->qkv && d->ab_dtype == KD_DTYPE_BF16,
                      "gemm row_stats: K-major bf16 operands, bf16 C, no bias / act / residual / aux / accumulate");
@@ -2406,271 +2495,202 @@ int launch_gemm(const kd_gemm_desc* d, void* stream_) {
                        "gemm row_stats: N and row_stats_vs multiples of 8, the tiled kernels' shapes");
         KD_CHECK_ARG(d->row_stats_inv_t > 0.f, "gemm row_stats: row_stats_inv_t must be > 0");
         KD_CHECK_ALIGN(d->row_stats, 16, "gemm row_stats: 16-B aligned");
-        GemmP pk = p;
-        pk.rst = d->row_stats; pk.rst_nt = ceil_div(d->N, 256); pk.rst_vs = d->row_stats_vs;
-        pk.rst_inv_t = d->row_stats_inv_t; pk.rst_top2 = d->row_stats_top2 ? 1 : 0;
-        pk.gm = pick_gm(ceil_div(d->M, 256), ceil_div(d->N, 256));
-        const dim3 grid(ceil_div(d->M, 256) * ceil_div(d->N, 256), 1);
-        pk.gx = (int)grid.x; pk.gy = 1; pk.tile0 = 0;
-        hipLaunchKernelGGL((k_gemm8<false, false, 32>), grid, dim3(NTH8), (gemm2_lds<256, 256>()), st, pk);
+        p.rst = d->row_stats; p.rst_nt = tiles_n8; p.rst_vs = d->row_stats_vs;
+        p.rst_inv_t = d->row_stats_inv_t; p.rst_top2 = d->row_stats_top2 ? 1 : 0;
+        hipLaunchKernelGGL((k_gemm8<false, false, G8_ROWSTATS>), grid8, dim3(NTH8), lds8, st, p);
         KD_LAUNCH_CHECK("k_gemm8 (row stats)");
         return KD_OK;
-    }
-    if (d->act == KD_ACT_SWIGLU) {   // fused gate|up GEMM + silu(gate) * up, on v8
+    case Route::SWIGLU: case Route::SWIGLU_PRETILED: case Route::SWIGLU_STREAMK:   // fused gate|up GEMM + silu(gate) * up
         KD_CHECK_SHAPE(d->N % 256 == 0 && d->M >= 1, "gemm swiglu: N = 2I needs I % 128 == 0");
         KD_CHECK_ARG(!d->bias && !d->residual && !d->accumulate && d->split_k <= 1,
                      "gemm swiglu: no bias / residual / accumulate / split-K");
         KD_CHECK_ARG(!amn && !bmn && d->c_dtype == KD_DTYPE_BF16 && c_ok16 && d->ldc >= d->N / 2,
                      "gemm swiglu: K-major operands, 16-B aligned bf16 output [M, N/2]");
         KD_CHECK_ARG(!d->aux || (d->ld_aux % 8 == 0 && (uintptr_t)d->aux % 16 == 0), "gemm swiglu: aux alignment");
-        GemmP pk = p;
-        pk.glu = d->N / 2; pk.act = KD_ACT_NONE;
-        pk.gm = pick_gm(ceil_div(d->M, 256), d->N / 256);
-        const dim3 grid(ceil_div(d->M, 256) * (d->N / 256), 1);
-        pk.gx = (int)grid.x; pk.gy = 1;
+        p.glu = d->N / 2; p.act = KD_ACT_NONE;
 #ifdef KD_AB_BUILD
-        if (d->variant == 20) hipLaunchKernelGGL((k_gemm9<false, false>), grid, dim3(NTH9), (gemm2_lds<256, 256>()), st, pk);
-        else if (!d->b_pretiled && use_v11(d->variant)) hipLaunchKernelGGL((k_gemm11<4>), grid, dim3(NTH8), (gemm2_lds<256, 256>()), st, pk);
-        else if (d->variant == 27) hipLaunchKernelGGL((k_gemm12<4 | 256>), grid, dim3(NTH8), (gemm2_lds<256, 256>()), st, pk);
-        else if (!d->b_pretiled && use_v12(d->variant)) hipLaunchKernelGGL((k_gemm12<4>), grid, dim3(NTH8), (gemm2_lds<256, 256>()), st, pk);
+        if (d->variant == 20) hipLaunchKernelGGL((k_gemm9<false, false>), grid8, dim3(NTH9), lds8, st, p);
+        else if (!d->b_pretiled && use_v11(d->variant)) hipLaunchKernelGGL((k_gemm11<G8_SWIGLU>), grid8, dim3(NTH8), lds8, st, p);
+        else if (d->variant == 27) hipLaunchKernelGGL((k_gemm12<G8_SWIGLU | G12_NOBARRIER>), grid8, dim3(NTH8), lds8, st, p);
+        else if (!d->b_pretiled && use_v12(d->variant)) hipLaunchKernelGGL((k_gemm12<G8_SWIGLU>), grid8, dim3(NTH8), lds8, st, p);
         else if (d->variant == 22)
-            hipLaunchKernelGGL((k_gemm8<false, false, 12>), grid, dim3(NTH8), (gemm2_lds<256, 256>()), st, pk);
+            hipLaunchKernelGGL((k_gemm8<false, false, G8_SWIGLU | G8_REGSTAGE>), grid8, dim3(NTH8), lds8, st, p);
         else if (d->variant == 28) {   // stamp build: per-wave cycle totals to the workspace (tools/stamp_glu.py)
-            KD_CHECK_ARG(d->workspace && d->workspace_bytes >= (uint64_t)grid.x * (4 * 8 + 4) * 4, "gemm swiglu stamps: workspace");
-            pk.sk_ws = (float*)d->workspace;
-            hipLaunchKernelGGL((k_gemm8<false, false, 5>), grid, dim3(NTH8), (gemm2_lds<256, 256>()), st, pk);
+            KD_CHECK_ARG(d->workspace && d->workspace_bytes >= (uint64_t)grid8.x * (4 * 8 + 4) * 4, "gemm swiglu stamps: workspace");
+            p.sk_ws = (float*)d->workspace;
+            hipLaunchKernelGGL((k_gemm8<false, false, G8_SWIGLU | G8_STAMP>), grid8, dim3(NTH8), lds8, st, p);
         }
-        else if (glu_epi_v0()) hipLaunchKernelGGL((k_gemm8<false, false, 4 | 512>), grid, dim3(NTH8), (gemm2_lds<256, 256>()), st, pk);
+        else if (glu_epi_v0()) hipLaunchKernelGGL((k_gemm8<false, false, G8_SWIGLU | G8_GLU_V0>), grid8, dim3(NTH8), lds8, st, p);
         else
 #endif
-        if (d->b_pretiled) hipLaunchKernelGGL((k_gemm8<false, false, 4 | 256>), grid, dim3(NTH8), (gemm2_lds<256, 256>()), st, pk);
-        else if (d->variant == 21 && sk_fits(grid.x, ceil_div(d->K, BK2), d)) {   // stream-K (v8 SwiGLU build)
-            if (const int rc = sk_setup(pk, grid.x, d, st); rc != KD_OK) return rc;
-            hipLaunchKernelGGL((k_gemm8<false, false, 4 | 1024>), dim3(pk.gx), dim3(NTH8), (gemm2_lds<256, 256>()), st, pk);
+        if (rt.route == Route::SWIGLU_PRETILED)
+            hipLaunchKernelGGL((k_gemm8<false, false, G8_SWIGLU | G8_PRETILED>), grid8, dim3(NTH8), lds8, st, p);
+        else if (rt.route == Route::SWIGLU_STREAMK) {
+            if (const int rc = sk_setup(p, grid8.x, d, st); rc != KD_OK) return rc;
+            hipLaunchKernelGGL((k_gemm8<false, false, G8_SWIGLU | G8_STREAMK>), dim3(p.gx), dim3(NTH8), lds8, st, p);
         }
-        else hipLaunchKernelGGL((k_gemm8<false, false, 4>), grid, dim3(NTH8), (gemm2_lds<256, 256>()), st, pk);
+        else hipLaunchKernelGGL((k_gemm8<false, false, G8_SWIGLU>), grid8, dim3(NTH8), lds8, st, p);
         KD_LAUNCH_CHECK("k_gemm<swiglu>");
         return KD_OK;
-    }
-    if (d->b_pretiled) {   // the v8 kernel over every tile, unsplit (the pre-tiled layout is per 256-row tile)
+    case Route::PRETILED:   // the pre-tiled layout is per 256-row tile
         KD_CHECK_ARG(d->N % 8 == 0 && c_ok16, "gemm b_pretiled: N % 8 == 0 and 16-B aligned C / residual rows");
-        GemmP q = p;
-        q.gm = pick_gm(ceil_div(d->M, 256), ceil_div(d->N, 256));
-        const dim3 grid(ceil_div(d->M, 256) * ceil_div(d->N, 256), 1);
-        q.gx = (int)grid.x; q.gy = 1; q.tile0 = 0;
-        hipLaunchKernelGGL((k_gemm8<false, false, 256>), grid, dim3(NTH8), (gemm2_lds<256, 256>()), st, q);
+        hipLaunchKernelGGL((k_gemm8<false, false, G8_PRETILED>), grid8, dim3(NTH8), lds8, st, p);
         KD_LAUNCH_CHECK("k_gemm8 (b_pretiled)");
         return KD_OK;
-    }
+    case Route::V8N: {
 #ifdef KD_AB_BUILD
-    // v8n (256x128, two workgroups per CU), forced (variant 30); K-major operands, unsplit.  As the
-    // auto choice for SigLIP's q|k|v scatter (62.5 vs 71.2 us alone, profiles/r05/v8n_qkv_ab.txt) the
-    // c1 step measured no faster (29.05-29.09 vs 29.08-29.13 samples/s), so the plan does not use it
-    if (d->variant == 30) {
-        // the q|k|v scatter takes 128-column tiles when a RoPE pair never straddles them (no RoPE, or
+        // v8n (256x128, two workgroups per CU), forced (variant 30); K-major operands, unsplit.  As the
+        // auto choice for SigLIP's q|k|v scatter (62.5 vs 71.2 us alone, profiles/r05/v8n_qkv_ab.txt) the
+        // c1 step measured no faster (29.05-29.09 vs 29.08-29.13 samples/s), so the plan does not use it.
+        // The q|k|v scatter takes 128-column tiles when a RoPE pair never straddles them (no RoPE, or
         // 128 % head_dim == 0: a tile is whole heads)
         KD_CHECK_ARG(!amn && !bmn && (!d->qkv || !d->qkv->cos_t || 128 % d->qkv->hd == 0) && !d->row_stats &&
                      !d->b_pretiled && !dact && d->act != KD_ACT_SWIGLU && d->split_k <= 1 && d->N % 8 == 0 && c_ok16,
                      "gemm variant 30 (v8n): K-major A and B, no SwiGLU / backward activation / row statistics / split, "
                      "N % 8 == 0; a RoPE q|k|v scatter needs 128 % head_dim == 0");
-        GemmP q = p;
-        q.gm = pick_gm(ceil_div(d->M, 256), ceil_div(d->N, 128));
-        q.stag_g = pick_gm(ceil_div(d->M, 256), ceil_div(d->N, 256));   // v8's row groups: v8's bits
-        const dim3 grid(ceil_div(d->M, 256) * ceil_div(d->N, 128), 1);
-        q.gx = (int)grid.x; q.gy = 1; q.tile0 = 0;
-        hipLaunchKernelGGL((k_gemm8n<0>), grid, dim3(NTH8), (gemm2_lds<256, 128, NS8N>()), st, q);
+        p.gm = pick_gm(tiles_m8, ceil_div(d->N, 128));
+        p.stag_g = pick_gm(tiles_m8, tiles_n8);   // v8's row groups: v8's bits
+        p.gx = tiles_m8 * ceil_div(d->N, 128);
+        hipLaunchKernelGGL((k_gemm8n<0>), dim3(p.gx), dim3(NTH8), (gemm2_lds<256, 128, NS8N>()), st, p);
         KD_LAUNCH_CHECK("k_gemm8n");
+#endif
         return KD_OK;
     }
-#endif
-    const int force = d->variant;   // 0 auto, 1 v1 128x128, 2/5 v3 256x256, 3/6 v3 256x128, 4/7 v3 128x256,
-                                    // 16 v8 256x256 (4 waves, AGPR accumulators), 17-19 v8 diagnostics, 22 v8 register-staged (negative result, kept for A/B)
-    if (force != 1 && big_ok) {
-        const GemmPlan pl = plan_gemm(d, d->workspace ? d->workspace_bytes : 0);
-        const int tbm = pl.var == 4 ? 128 : 256, tbn = pl.var == 3 ? 128 : 256;
-        const int tiles = ceil_div(d->M, tbm) * ceil_div(d->N, tbn);
-        p.gm = pick_gm(ceil_div(d->M, tbm), ceil_div(d->N, tbn));
-        if (pl.var == 21) {   // stream-K (v8): whole waves data-parallel, the rest in runs, folded in-launch
-            GemmP q = p;
-            if (const int rc = sk_setup(q, tiles, d, st); rc != KD_OK) return rc;
-            const size_t lds = gemm2_lds<256, 256>();
-            const dim3 grid(q.gx);
-            if (!amn && !bmn) hipLaunchKernelGGL((k_gemm8<false, false, 1024>), grid, dim3(NTH8), lds, st, q);
-            else if (!amn && bmn) hipLaunchKernelGGL((k_gemm8<false, true, 1024>), grid, dim3(NTH8), lds, st, q);
-            else if (amn && bmn) hipLaunchKernelGGL((k_gemm8<true, true, 1024>), grid, dim3(NTH8), lds, st, q);
-            else hipLaunchKernelGGL((k_gemm8<true, false, 1024>), grid, dim3(NTH8), lds, st, q);
-            KD_LAUNCH_CHECK("k_gemm8 (stream-K)");
-            return KD_OK;
-        }
-        // one launch of the planned kernel over linear tiles [q.tile0, q.tile0 + nt), gy K splits
-        auto launch_tiles = [&](const GemmP& q0, int nt, unsigned gy) {
-            const dim3 grid((unsigned)nt, gy);
-            GemmP q = q0;
-            q.gx = nt; q.gy = (int)gy;
-#ifdef KD_AB_BUILD
-            if (pl.var == 20) {   // v9
-                const size_t lds = gemm2_lds<256, 256>();
-                if (!amn && !bmn) hipLaunchKernelGGL((k_gemm9<false, false>), grid, dim3(NTH9), lds, st, q);
-                else if (!amn && bmn) hipLaunchKernelGGL((k_gemm9<false, true>), grid, dim3(NTH9), lds, st, q);
-                else if (amn && bmn) hipLaunchKernelGGL((k_gemm9<true, true>), grid, dim3(NTH9), lds, st, q);
-                else hipLaunchKernelGGL((k_gemm9<true, false>), grid, dim3(NTH9), lds, st, q);
-            } else
-#endif
-            if (pl.var == 16) {   // v8; forced variants 17-19 are its diagnostic builds (EXP bits above)
-                const size_t lds = gemm2_lds<256, 256>();
-#define L8(E)                                                                                                   \
-    {                                                                                                           \
-        if (!amn && !bmn) hipLaunchKernelGGL((k_gemm8<false, false, E>), grid, dim3(NTH8), lds, st, q);         \
-        else if (!amn && bmn) hipLaunchKernelGGL((k_gemm8<false, true, E>), grid, dim3(NTH8), lds, st, q);      \
-        else if (amn && bmn) hipLaunchKernelGGL((k_gemm8<true, true, E>), grid, dim3(NTH8), lds, st, q);        \
-        else hipLaunchKernelGGL((k_gemm8<true, false, E>), grid, dim3(NTH8), lds, st, q);                       \
+    case Route::TILED: return launch_tiled(d, rt.plan, p, st);
+    case Route::V1: return launch_v1(d, p, st);
     }
-#define L8K(E)                                                                                                  \
-    {                                                                                                           \
-        if (!amn && !bmn) hipLaunchKernelGGL((k_gemm8<false, false, E>), grid, dim3(NTH8), lds, st, q);         \
-        else L8(0)                                                                                              \
-    }
-#ifdef KD_AB_BUILD
-                if (!amn && !bmn && use_v11(force)) {   // v11: the same tiles on 32x32x16 MFMAs
-                    hipLaunchKernelGGL((k_gemm11<0>), grid, dim3(NTH8), lds, st, q);
-                    return;
-                }
-                if (!amn && !bmn && force == 27) {   // v12 without the odd-step barriers (A/B)
-                    hipLaunchKernelGGL((k_gemm12<256>), grid, dim3(NTH8), lds, st, q);
-                    return;
-                }
-                if (!amn && !bmn && use_v12(force)) {   // v12: the same tiles, whole-line K-major staging
-                    hipLaunchKernelGGL((k_gemm12<0>), grid, dim3(NTH8), lds, st, q);
-                    return;
-                }
-                switch (force) {   // the diagnostic builds exist for the forward (K-major x K-major) layout only
-                    case 17: L8(1) break;   // stamps: every layout
-                    case 18: L8K(2) break;
-                    case 19: L8K(64) break;
-                    case 22: L8K(8) break;
-                    default: L8(0) break;
-                }
-#else
-                L8(0)
-                (void)force;
-#endif
-#undef L8K
-#undef L8
-            } else {
-#define L3(BMv, BNv, AM, BMN) hipLaunchKernelGGL((k_gemm3<BMv, BNv, AM, BMN>), grid, dim3(NTH2), (gemm2_lds<BMv, BNv>()), st, q)
-#define L3SEL(BMv, BNv)                                     \
-    if (!amn && !bmn) L3(BMv, BNv, false, false);           \
-    else if (!amn && bmn) L3(BMv, BNv, false, true);        \
-    else if (amn && bmn) L3(BMv, BNv, true, true);          \
-    else L3(BMv, BNv, true, false);
-                if (pl.var == 2) { L3SEL(256, 256) }
-                else if (pl.var == 3) { L3SEL(256, 128) }
-                else { L3SEL(128, 256) }
-#undef L3SEL
-#undef L3
-            }
-        };
-        if (pl.split <= 1) {
-            p.tile0 = 0;
-            launch_tiles(p, tiles, 1);
-            KD_LAUNCH_CHECK("k_gemm (tiles)");
-            return KD_OK;
-        }
-        KD_CHECK_ARG(d->workspace && d->workspace_bytes >= (uint64_t)pl.split * d->M * d->N * 4,
-                     "gemm: split-K workspace too small");
-        if (pl.dp_tiles > 0) {   // hybrid: whole waves unsplit with the full epilogue
-            p.tile0 = 0;
-            launch_tiles(p, pl.dp_tiles, 1);
-            KD_LAUNCH_CHECK("k_gemm (whole waves)");
-        }
-        if (force == 32 && pl.var == 16) {   // v8 split tiles folded in-launch (no planes, no reduce launch)
-            const int nt = tiles - pl.dp_tiles;
-            const size_t cnt_b = sk_cnt_bytes(nt);
-            KD_CHECK_ARG(d->workspace_bytes >= cnt_b + (size_t)nt * pl.split * SK_TILE_F32 * 4,
-                         "gemm: split-K fold workspace too small");
-            GemmP q = p;
-            q.kchunk = pl.kchunk; q.tile0 = pl.dp_tiles; q.gx = nt; q.gy = pl.split;
-            q.sk_cnt = (int*)d->workspace; q.sk_ws = (float*)((char*)d->workspace + cnt_b);
-            if (hipMemsetAsync(q.sk_cnt, 0, cnt_b, st) != hipSuccess) return fail(KD_ERR_LAUNCH, "gemm: split-K ticket memset");
-            const dim3 grid((unsigned)nt, (unsigned)pl.split);
-            const size_t lds = gemm2_lds<256, 256>();
-            if (!amn && !bmn) hipLaunchKernelGGL((k_gemm8<false, false, 2048>), grid, dim3(NTH8), lds, st, q);
-            else if (!amn && bmn) hipLaunchKernelGGL((k_gemm8<false, true, 2048>), grid, dim3(NTH8), lds, st, q);
-            else if (amn && bmn) hipLaunchKernelGGL((k_gemm8<true, true, 2048>), grid, dim3(NTH8), lds, st, q);
-            else hipLaunchKernelGGL((k_gemm8<true, false, 2048>), grid, dim3(NTH8), lds, st, q);
-            KD_LAUNCH_CHECK("k_gemm8 (split-K fold)");
-            return KD_OK;
-        }
-        GemmP pk = p;   // the split tiles write plain fp32 partial planes
-        pk.C = d->workspace; pk.ldc = d->N; pk.c_f32 = 1; pk.accumulate = 0; pk.alpha = 1.f;
-        pk.alpha_dev = nullptr; pk.bias = nullptr; pk.aux = nullptr; pk.resid = nullptr; pk.act = KD_ACT_NONE;
-        pk.kchunk = pl.kchunk; pk.split_stride = (int64_t)d->M * d->N; pk.tile0 = pl.dp_tiles;
-        launch_tiles(pk, tiles - pl.dp_tiles, (unsigned)pl.split);
-        KD_LAUNCH_CHECK("k_gemm (split tiles)");
-        p.split_stride = (int64_t)d->M * d->N;
-        p.tile0 = pl.dp_tiles;
-        p.gx = tiles - pl.dp_tiles; p.gy = tbm * tbn / 1024;
-        // one float4 column chunk per thread: BM / (1024 / BN) row slabs of 1024 / BN rows per tile
-        hipLaunchKernelGGL(k_splitk_reduce, dim3(reduce_grid(p.gx * p.gy)), dim3(256), 0, st,
-                           (const float*)d->workspace, pl.split, p, tbm, tbn);
-        KD_LAUNCH_CHECK("k_splitk_reduce");
+    return KD_OK;
+}
+
+// the planned tiled kernel: VARIANTS' codes 2-7 the v3 tiles, 16 / 24 v8 256x256 (4 waves, AGPR
+// accumulators), 21 stream-K, 32 the in-launch fold; A/B library: 17-19 / 22 v8's diagnostic and
+// register-staged builds, 20 v9, 23 v11, 26 / 27 v12
+static int launch_tiled(const kd_gemm_desc* d, const GemmPlan& pl, GemmP& p, hipStream_t st) {
+    const int li = layout_index(d->a_layout == KD_LAYOUT_MN_MAJOR, d->b_layout == KD_LAYOUT_MN_MAJOR);
+    const size_t lds8 = gemm2_lds<256, 256>();
+    const int force = d->variant;
+    const int tbm = pl.var == 4 ? 128 : 256, tbn = pl.var == 3 ? 128 : 256;
+    const int tiles = ceil_div(d->M, tbm) * ceil_div(d->N, tbn);
+    p.gm = pick_gm(ceil_div(d->M, tbm), ceil_div(d->N, tbn));
+    if (pl.var == 21) {   // stream-K (v8): whole waves data-parallel, the rest in runs, folded in-launch
+        if (const int rc = sk_setup(p, tiles, d, st); rc != KD_OK) return rc;
+        hipLaunchKernelGGL(V8<G8_STREAMK>[li], dim3(p.gx), dim3(NTH8), lds8, st, p);
+        KD_LAUNCH_CHECK("k_gemm8 (stream-K)");
         return KD_OK;
     }
-    const int tiles = ceil_div(d->M, BM) * ceil_div(d->N, BN);
-    const size_t smem = 4 * TILE_BYTES;
-    p.gx = tiles; p.gy = 1;
-    if (!amn && !bmn) hipLaunchKernelGGL((k_gemm<false, false>), dim3(tiles), dim3(NTH), smem, st, p);
-    else if (!amn && bmn) hipLaunchKernelGGL((k_gemm<false, true>), dim3(tiles), dim3(NTH), smem, st, p);
-    else if (amn && bmn) hipLaunchKernelGGL((k_gemm<true, true>), dim3(tiles), dim3(NTH), smem, st, p);
-    else hipLaunchKernelGGL((k_gemm<true, false>), dim3(tiles), dim3(NTH), smem, st, p);
+    // one launch of the planned kernel over linear tiles [q.tile0, q.tile0 + nt), gy K splits
+    auto launch_tiles = [&](const GemmP& q0, int nt, unsigned gy) {
+        GemmP q = q0;
+        q.gx = nt; q.gy = (int)gy;
+        GemmKernel k = nullptr;
+        unsigned nth = NTH8;
+        size_t lds = lds8;
+#ifdef KD_AB_BUILD
+        static constexpr GemmKernel V9[4] = {k_gemm9<false, false>, k_gemm9<false, true>, k_gemm9<true, true>, k_gemm9<true, false>};
+        // v8's diagnostic builds: all but the stamps exist for K-major x K-major only, the other layouts run
+        // plain v8 (these lines' order is the order of the builds in the object, which is compared byte for byte)
+        const int diag = variant_info(force)->flags;
+        if (pl.var == 20) { k = V9[li]; nth = NTH9; }
+        else if (pl.var != 16) {}
+        else if (li == 0 && use_v11(force)) k = k_gemm11<0>;   // the same tiles on 32x32x16 MFMAs
+        else if (li == 0 && force == 27) k = k_gemm12<G12_NOBARRIER>;
+        else if (li == 0 && use_v12(force)) k = k_gemm12<0>;   // the same tiles, whole-line K-major staging
+        else if (diag == G8_STAMP) k = V8<G8_STAMP>[li];
+        else if (diag == G8_NODMA && li == 0) k = k_gemm8<false, false, G8_NODMA>;
+        else if (li != 0) k = V8<0>[li];
+        else if (diag == G8_HOT) k = k_gemm8<false, false, G8_HOT>;
+        else if (diag == G8_REGSTAGE) k = k_gemm8<false, false, G8_REGSTAGE>;
+#endif
+        if (k) {}
+        else if (pl.var == 16) k = V8<0>[li];
+        else if (pl.var == 2) { k = V3<256, 256>[li]; nth = NTH2; }
+        else if (pl.var == 3) { k = V3<256, 128>[li]; nth = NTH2; lds = gemm2_lds<256, 128>(); }
+        else { k = V3<128, 256>[li]; nth = NTH2; lds = gemm2_lds<128, 256>(); }
+        hipLaunchKernelGGL(k, dim3((unsigned)nt, gy), dim3(nth), lds, st, q);
+    };
+    if (pl.split <= 1) {
+        launch_tiles(p, tiles, 1);
+        KD_LAUNCH_CHECK("k_gemm (tiles)");
+        return KD_OK;
+    }
+    KD_CHECK_ARG(d->workspace && d->workspace_bytes >= (uint64_t)pl.split * d->M * d->N * 4,
+                 "gemm: split-K workspace too small");
+    if (pl.dp_tiles > 0) {   // hybrid: whole waves unsplit with the full epilogue
+        launch_tiles(p, pl.dp_tiles, 1);
+        KD_LAUNCH_CHECK("k_gemm (whole waves)");
+    }
+    if (force == 32 && pl.var == 16) {   // v8 split tiles folded in-launch (no planes, no reduce launch)
+        const int nt = tiles - pl.dp_tiles;
+        const size_t cnt_b = sk_cnt_bytes(nt);
+        KD_CHECK_ARG(d->workspace_bytes >= cnt_b + (size_t)nt * pl.split * SK_TILE_F32 * 4,
+                     "gemm: split-K fold workspace too small");
+        GemmP q = p;
+        q.kchunk = pl.kchunk; q.tile0 = pl.dp_tiles; q.gx = nt; q.gy = pl.split;
+        q.sk_cnt = (int*)d->workspace; q.sk_ws = (float*)((char*)d->workspace + cnt_b);
+        if (hipMemsetAsync(q.sk_cnt, 0, cnt_b, st) != hipSuccess) return fail(KD_ERR_LAUNCH, "gemm: split-K ticket memset");
+        hipLaunchKernelGGL(V8<G8_FOLD>[li], dim3((unsigned)nt, (unsigned)pl.split), dim3(NTH8), lds8, st, q);
+        KD_LAUNCH_CHECK("k_gemm8 (split-K fold)");
+        return KD_OK;
+    }
+    GemmP pk = p;   // the split tiles write plain fp32 partial planes
+    pk.C = d->workspace; pk.ldc = d->N; pk.c_f32 = 1; pk.accumulate = 0; pk.alpha = 1.f;
+    pk.alpha_dev = nullptr; pk.bias = nullptr; pk.aux = nullptr; pk.resid = nullptr; pk.act = KD_ACT_NONE;
+    pk.kchunk = pl.kchunk; pk.split_stride = (int64_t)d->M * d->N; pk.tile0 = pl.dp_tiles;
+    launch_tiles(pk, tiles - pl.dp_tiles, (unsigned)pl.split);
+    KD_LAUNCH_CHECK("k_gemm (split tiles)");
+    p.split_stride = (int64_t)d->M * d->N;
+    p.tile0 = pl.dp_tiles;
+    p.gx = tiles - pl.dp_tiles; p.gy = tbm * tbn / 1024;
+    // one float4 column chunk per thread: BM / (1024 / BN) row slabs of 1024 / BN rows per tile
+    hipLaunchKernelGGL(k_splitk_reduce, dim3(reduce_grid(p.gx * p.gy)), dim3(256), 0, st,
+                       (const float*)d->workspace, pl.split, p, tbm, tbn);
+    KD_LAUNCH_CHECK("k_splitk_reduce");
+    return KD_OK;
+}
+
+static int launch_v1(const kd_gemm_desc* d, GemmP& p, hipStream_t st) {
+    static constexpr GemmKernel V1[4] = {k_gemm<false, false>, k_gemm<false, true>, k_gemm<true, true>, k_gemm<true, false>};
+    p.gx = ceil_div(d->M, BM) * ceil_div(d->N, BN); p.gm = 0;   // 128 x 128 tiles in the default group height
+    hipLaunchKernelGGL(V1[layout_index(d->a_layout == KD_LAYOUT_MN_MAJOR, d->b_layout == KD_LAYOUT_MN_MAJOR)], dim3(p.gx),
+                       dim3(NTH), 4 * TILE_BYTES, st, p);
     KD_LAUNCH_CHECK("k_gemm");
     return KD_OK;
 }
 
-// what one member of a grouped launch must be (launch_gemm_group checks the same, with messages):
-// a plain weight gradient the 256 x 256 v8 tile kernel takes -- MN-major x MN-major bf16 operands,
-// fp32 C, no bias / activation / residual / aux, the v8 loads' alignments
-bool gemm_group_member_ok(const kd_gemm_desc* d) {
-    return d && d->A && d->B && d->C && d->M >= 128 && d->N >= 128 && d->K > 0 &&
-           d->a_layout == KD_LAYOUT_MN_MAJOR && d->b_layout == KD_LAYOUT_MN_MAJOR && d->ab_dtype == KD_DTYPE_BF16 &&
-           d->c_dtype == KD_DTYPE_F32 && !d->bias && d->act == KD_ACT_NONE && !d->residual && !d->aux && !d->qkv &&
-           !d->row_stats && !d->alpha_dev && !d->b_pretiled && d->M % 8 == 0 && d->N % 8 == 0 && d->lda % 8 == 0 &&
-           d->ldb % 8 == 0 && d->ldc % 8 == 0 && d->lda >= d->M && d->ldb >= d->N && d->ldc >= d->N &&
-           (uintptr_t)d->A % 16 == 0 && (uintptr_t)d->B % 16 == 0 && (uintptr_t)d->C % 16 == 0 &&
-           (uint64_t)256 * d->lda * 2 < 0x7FFFFFFFull && (uint64_t)256 * d->ldb * 2 < 0x7FFFFFFFull;
+// What one member of a grouped launch must be: a plain weight gradient the 256 x 256 v8 tile kernel
+// takes -- MN-major x MN-major bf16 operands, fp32 C, no bias / activation / residual / aux, the v8
+// loads' alignments.  The first check it fails, or nullptr.
+static const char* gemm_group_member_fault(const kd_gemm_desc* d) {
+    if (!d) return "gemm group: null member";
+    if (!(d->A && d->B && d->C)) return "gemm group: null operand";
+    if (!(d->M > 0 && d->N > 0 && d->K > 0)) return "gemm group: empty shape";
+    if (!(d->a_layout == KD_LAYOUT_MN_MAJOR && d->b_layout == KD_LAYOUT_MN_MAJOR))
+        return "gemm group: MN-major A and B only (weight gradients)";
+    if (!(d->ab_dtype == KD_DTYPE_BF16 && d->c_dtype == KD_DTYPE_F32)) return "gemm group: bf16 operands, fp32 C";
+    if (d->bias || d->act != KD_ACT_NONE || d->residual || d->aux || d->qkv || d->row_stats || d->alpha_dev || d->b_pretiled)
+        return "gemm group: no bias / activation / residual / aux / scatter / row statistics / device alpha";
+    if (!(d->M % 8 == 0 && d->N % 8 == 0)) return "gemm group: M % 8 == 0 and N % 8 == 0";
+    if (!(d->M >= 128 && d->N >= 128)) return "gemm group: M, N >= 128 (the 256 x 256 tile kernel)";
+    if (!(d->lda % 8 == 0 && d->ldb % 8 == 0 && d->ldc % 8 == 0 && d->lda >= d->M && d->ldb >= d->N && d->ldc >= d->N))
+        return "gemm group: lda >= M, ldb >= N, ldc >= N, multiples of 8";
+    if (!((uintptr_t)d->A % 16 == 0 && (uintptr_t)d->B % 16 == 0 && (uintptr_t)d->C % 16 == 0))
+        return "gemm group: A, B and C must be 16-B aligned";
+    if (!((uint64_t)256 * d->lda * 2 < 0x7FFFFFFFull && (uint64_t)256 * d->ldb * 2 < 0x7FFFFFFFull))
+        return "gemm group: leading dimension too large for 31-bit buffer records";
+    return nullptr;
 }
+bool gemm_group_member_ok(const kd_gemm_desc* d) { return gemm_group_member_fault(d) == nullptr; }
 
 int launch_gemm_group(const kd_gemm_desc* const* ds, int n, void* stream_) {
     KD_CHECK_ARG(ds != nullptr, "gemm group: null member list");
     KD_CHECK_ARG(n >= 1 && n <= GROUP_MAX, "gemm group: 1 to 4 members");
-    GemmGroupP g;
-    std::memset(&g, 0, sizeof(g));
+    GemmGroupP g{};
     int total = 0;
     for (int i = 0; i < n; ++i) {
         const kd_gemm_desc* d = ds[i];
-        KD_CHECK_ARG(d != nullptr, "gemm group: null member");
-        KD_CHECK_ARG(d->A && d->B && d->C, "gemm group: null operand");
-        KD_CHECK_ARG(d->M > 0 && d->N > 0 && d->K > 0, "gemm group: empty shape");
-        KD_CHECK_ARG(d->a_layout == KD_LAYOUT_MN_MAJOR && d->b_layout == KD_LAYOUT_MN_MAJOR,
-                     "gemm group: MN-major A and B only (weight gradients)");
-        KD_CHECK_ARG(d->ab_dtype == KD_DTYPE_BF16 && d->c_dtype == KD_DTYPE_F32, "gemm group: bf16 operands, fp32 C");
-        KD_CHECK_ARG(!d->bias && d->act == KD_ACT_NONE && !d->residual && !d->aux && !d->qkv && !d->row_stats &&
-                     !d->alpha_dev && !d->b_pretiled,
-                     "gemm group: no bias / activation / residual / aux / scatter / row statistics / device alpha");
-        KD_CHECK_ARG(d->M % 8 == 0 && d->N % 8 == 0, "gemm group: M % 8 == 0 and N % 8 == 0");
-        KD_CHECK_ARG(d->M >= 128 && d->N >= 128, "gemm group: M, N >= 128 (the 256 x 256 tile kernel)");
-        KD_CHECK_ARG(d->lda % 8 == 0 && d->ldb % 8 == 0 && d->ldc % 8 == 0 && d->lda >= d->M && d->ldb >= d->N &&
-                     d->ldc >= d->N, "gemm group: lda >= M, ldb >= N, ldc >= N, multiples of 8");
-        KD_CHECK_ARG((uintptr_t)d->A % 16 == 0 && (uintptr_t)d->B % 16 == 0 && (uintptr_t)d->C % 16 == 0,
-                     "gemm group: A, B and C must be 16-B aligned");
-        KD_CHECK_ARG((uint64_t)256 * d->lda * 2 < 0x7FFFFFFFull && (uint64_t)256 * d->ldb * 2 < 0x7FFFFFFFull,
-                     "gemm group: leading dimension too large for 31-bit buffer records");
+        if (const char* fault = gemm_group_member_fault(d)) return fail(KD_ERR_ARG, fault);
         GemmP& p = g.p[i];   // launch_gemm's parameters of this member on v8, unsplit
-        p.A = (const bf16*)d->A; p.B = (const bf16*)d->B; p.C = d->C;
-        p.lda = d->lda; p.ldb = d->ldb; p.ldc = d->ldc;
-        p.M = d->M; p.N = d->N; p.K = d->K; p.alpha = d->alpha;
-        p.c_f32 = 1; p.accumulate = d->accumulate;
-        p.kchunk = d->K; p.gy = 1; p.rst_inv_t = 1.f;
+        p = make_params(d);
         p.stagger = ab_knob("KD_GEMM_STAGGER", 1);
         const int tiles_m = ceil_div(d->M, 256), tiles_n = ceil_div(d->N, 256);
         p.gm = pick_gm(tiles_m, tiles_n);
@@ -2687,16 +2707,7 @@ int launch_gemm_group(const kd_gemm_desc* const* ds, int n, void* stream_) {
 int gemm_plan_query(const kd_gemm_desc* d, int32_t* var, int32_t* split, int32_t* dp) {
     KD_CHECK_ARG(d && var && split && dp, "gemm_plan: null pointer");
     KD_CHECK_SHAPE(d->M > 0 && d->N > 0 && d->K > 0, "gemm_plan: empty shape");
-    const bool amn = d->a_layout == KD_LAYOUT_MN_MAJOR, bmn = d->b_layout == KD_LAYOUT_MN_MAJOR;
-    const bool big_ok = d->N % 8 == 0 && d->M >= 128 && d->N >= 128 &&
-                        ((uint64_t)d->M * d->N >= (1ull << 20) || (d->workspace && d->K >= 2048 && d->split_k != 1)) &&
-                        (!amn || d->M % 8 == 0) && (!bmn || d->N % 8 == 0);
-    if (d->act == KD_ACT_SWIGLU) { *var = 16; *split = 1; *dp = 0; return KD_OK; }
-#ifdef KD_AB_BUILD
-    if (d->variant == 30) { *var = 30; *split = 1; *dp = 0; return KD_OK; }   // v8n (launch_gemm)
-#endif
-    if (d->variant == 1 || !big_ok) { *var = 1; *split = 1; *dp = 0; return KD_OK; }
-    const GemmPlan pl = plan_gemm(d, d->workspace ? d->workspace_bytes : 0);
+    const GemmPlan pl = gemm_route(d).plan;
     *var = pl.var; *split = pl.split; *dp = pl.dp_tiles;
     return KD_OK;
 }

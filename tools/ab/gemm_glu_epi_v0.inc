@@ -3,7 +3,7 @@
 // file's internal helpers); the product libkdstep.so never compiles it.  Build: csrc/build.py --ab.
 
 
-// the round-4 SwiGLU epilogue before the packed rewrite (EXP bit 512 / KD_GLU_EPI_V0=1: A/B only)
+// the round-4 SwiGLU epilogue before the packed rewrite (G8_GLU_V0 / KD_GLU_EPI_V0=1: A/B only)
 template <int TM, int TN, int MT, int NT, int NTHR, bool L32 = false>
 __device__ __forceinline__ void epilogue_glu_v0(const GemmP& p, const f32x4 (&acc)[MT][NT], char* smem, int m0, int nb, int wm,
                                              int wn, int lane, int tid) {

@@ -44,11 +44,11 @@ __device__ __forceinline__ bf16x8 frag32(const char* tile, int rb, int h, int la
     return *(const bf16x8*)(tile + r * 64 + ((c ^ f4(r)) << 4));
 }
 
-// EXP bits as v8: 4 = the fused SwiGLU build, 32 = the lm_head row-statistics build
+// EXP: v8's build flags (gemm.hip G8_*), of which G8_SWIGLU and G8_ROWSTATS are built here
 template <int EXP>
 __device__ __forceinline__ void g11_tile(GemmP p, int tm, int tn, char* smem) {
-    constexpr bool RSTATS = EXP & 32;
-    constexpr bool glu = EXP & 4;
+    constexpr bool RSTATS = EXP & G8_ROWSTATS;
+    constexpr bool glu = EXP & G8_SWIGLU;
     constexpr int SA = 256 * BK2 * 2, SS = 2 * SA;
     const int tid = threadIdx.x, lane = tid & 63;
     const int wid = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -120,7 +120,6 @@ __device__ __forceinline__ void g11_tile(GemmP p, int tm, int tn, char* smem) {
     }
     KD_G11_SYNC()
     __builtin_amdgcn_sched_barrier(0);
-#define KD_SB __builtin_amdgcn_sched_barrier(0);
 #define KD_G11_STEP(SL, CA, CB, NA, NB, FT)                                                                  \
     {                                                                                                         \
         const int t_ = t + (SL);                                                                              \
@@ -161,7 +160,6 @@ __device__ __forceinline__ void g11_tile(GemmP p, int tm, int tn, char* smem) {
     if (rem > 2) KD_G11_STEP(2, xa, xb, ya, yb, PartT)
 #undef KD_G11_STEP
 #undef KD_G11_SYNC
-#undef KD_SB
     // drain the ring (out-of-range DMAs still write LDS) and the MFMA pipe before the
     // accumulators are read back (asm MFMAs are invisible to the hazard recognizer)
     asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)\n\ts_nop 15\n\ts_nop 15\n\ts_nop 15\n\ts_nop 15" ::: "memory");
@@ -215,16 +213,18 @@ __device__ __forceinline__ bf16x8 frag_pair(const char* img, int rb, int h, int 
     return *(const bf16x8*)(img + r * 128 + ((c ^ swp(r)) << 4));
 }
 
+constexpr int G12_NOBARRIER = 256;
 template <int EXP>
 __device__ __forceinline__ void g12_tile(GemmP p, int tm, int tn, char* smem) {
-    constexpr bool RSTATS = EXP & 32;
-    constexpr bool glu = EXP & 4;
-    // EXP & 256 (forced variant 27): no barrier at the end of odd steps.  The only cross-wave
+    constexpr bool RSTATS = EXP & G8_ROWSTATS;
+    constexpr bool glu = EXP & G8_SWIGLU;
+    // G12_NOBARRIER (forced variant 27; v12's own flag, the value v8 uses for pre-tiled B): no barrier
+    // at the end of odd steps.  The only cross-wave
     // hazards are per PAIR: RAW (pair q, issued in step 2q-3, is first read in step 2q-1: every
     // wave's vmcnt(0) + the barrier at the end of EVEN step 2q-2) and WAR (pair q+2 overwrites
     // pair q's slot in odd step 2q+1, after every wave's last read of pair q in step 2q: the
     // lgkmcnt(0) + barrier at the end of even step 2q); the odd-step barrier guards nothing.
-    constexpr bool NOB = EXP & 256;
+    constexpr bool NOB = EXP & G12_NOBARRIER;
     constexpr int PA = 256 * 128;       // one operand's pair image (32 KiB)
     constexpr int PS = 2 * PA;          // a pair slot (64 KiB); two of them
     const int tid = threadIdx.x, lane = tid & 63;
@@ -299,7 +299,6 @@ __device__ __forceinline__ void g12_tile(GemmP p, int tm, int tn, char* smem) {
         else wait_vm<0>();                                 \
         __builtin_amdgcn_s_barrier();                      \
     }
-#define KD_SB __builtin_amdgcn_sched_barrier(0);
     // step t + SL (SL = 0..3 of a group of four; t % 4 == 0): stage t+SL is in registers (CA, CB);
     // stage t+SL+1 is read from pair slot ((SL+1) >> 1) & 1, half (SL+1) & 1; odd SL issue pair
     // (t+SL+3)/2 into pair slot ((SL+3) >> 1) & 1
@@ -355,7 +354,6 @@ __device__ __forceinline__ void g12_tile(GemmP p, int tm, int tn, char* smem) {
     if (rem > 2) KD_G12_STEP(2, xa, xb, ya, yb, PartT)
 #undef KD_G12_STEP
 #undef KD_G12_SYNC
-#undef KD_SB
     asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)\n\ts_nop 15\n\ts_nop 15" ::: "memory");
     __builtin_amdgcn_sched_barrier(0);
     __syncthreads();

@@ -86,7 +86,6 @@ __device__ __forceinline__ void g8n_tile(GemmP p, int tm, int tn, char* smem) {
     }
     KD_G8N_SYNC()
     __builtin_amdgcn_sched_barrier(0);
-#define KD_SB __builtin_amdgcn_sched_barrier(0);
     // unit u: the 4 MFMAs of A fragment u; DMA u (u < 6); next-stage fragment reads: units 0-3 two
     // A fragments each, units 4-5 two B fragments each
 #define KD_G8N_STEP(SL, CA, CB, NA, NB, FT)                                                                  \
@@ -141,7 +140,6 @@ __device__ __forceinline__ void g8n_tile(GemmP p, int tm, int tn, char* smem) {
     if (rem > 4) { t += 3; KD_G8N_STEP(1, xa, xb, ya, yb, PartT) t -= 3; }
 #undef KD_G8N_STEP
 #undef KD_G8N_SYNC
-#undef KD_SB
     asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)\n\ts_nop 15\n\ts_nop 15" ::: "memory");
     __builtin_amdgcn_sched_barrier(0);
     __syncthreads();
