@@ -550,6 +550,47 @@ int kd_attn_extend(const void* q, const void* k_new, const void* v_new, void* k_
                    int nb, int rows, int H, int HKV, int hd, int hdp, int smax, const int32_t* row_start,
                    const int32_t* base, void* workspace, size_t workspace_bytes, void* stream);
 
+/* Constrained decoding (allowed_token_ids of generate() / generate_batch() / generate_grouped()):
+ * the token is chosen among A allowed ids only, as transformers chooses it when a user logits
+ * processor adds 0 to the allowed ids and -inf to every other one behind its own processors.
+ * `ids` is a device int32 array [A], ascending and unique, every id in [0, N_full).  The step then
+ * needs A logits, not V: the gathered GEMVs read the A allowed rows of the lm_head and
+ * kd_gen_select_ids searches A scores.  Stream-ordered, no host sync, no workspace, fixed arguments
+ * across steps (one captured graph replays the step), and batch invariant in the sense above.
+ * kd_gemv_gather: y [A] bf16, y[j] = x[K] . W[ids[j], :] (no epilogue, no fused norm: the lm_head
+ *   has neither).  kd_gemv_batch_gather: y [nb, A] bf16 contiguous, y[b, j] = x[b, :] . W[ids[j], :],
+ *   1 <= nb <= 16, x rows ldx apart.  W is the full [N_full, K] weight, rows ldw apart.  Element
+ *   (b, j) is bit-identical to kd_gemv / kd_gemv_batch with N = N_full at column ids[j]: the same
+ *   per-row arithmetic in the same order.  An id outside [0, N_full) reads nothing and scores -inf.
+ * kd_gemv_gather_supported(N_full, K): 1 where that promise holds, i.e. where the full routes'
+ *   order on a row does not depend on N: kd_gemv on its wave-per-row kernel (not N_full < 4096
+ *   with K >= 512) and kd_gemv_batch on one whole-K chain per 16-row tile (N_full > 32752 and
+ *   K <= 1536: no K shared among waves or workgroups); the second implies the first, and both
+ *   entries take that one set.  Elsewhere they return KD_ERR_SHAPE: run the full head and gather
+ *   its columns instead.
+ * kd_gen_select_ids: kd_gen_select_batch over compact scores [nb, A] bf16 (rows ld_scores >= A
+ *   apart, column j the score of token ids[j]), 1 <= nb <= 16, 1 <= A <= KD_GEN_ALLOWED_MAX.  The
+ *   repetition penalty applies to an allowed id that occurs in the row's sequence (prompt and
+ *   generated), the n-gram ban to an allowed id that would repeat an n-gram; ids of the sequence
+ *   that are not allowed matter as n-gram context only (each is looked up in `ids` by binary
+ *   search, a miss touches nothing, so the cost follows A and the row's length, never V).  The
+ *   choice is the allowed id with the largest processed fp32 score, the lowest id on a tie; NaN
+ *   never wins; if no allowed id is left with a score above -inf the choice is token 0, allowed or
+ *   not (the argmax of a row of V scores that are all -inf).  Writes as kd_gen_select_batch:
+ *   seq[b][cur_dev[b]], out[b] (optional), cur_dev[b] += 1; a full row (cur_dev[b] == smax) gets
+ *   out[b] and cur_dev[b] = smax + 1 but no element of seq.
+ *   Null pointers and penalty <= 0 or ngram < 0 -> KD_ERR_ARG; A, nb, smax or ld_scores out of
+ *   range -> KD_ERR_SHAPE; both before any device work. */
+#define KD_GEN_ALLOWED_MAX 16384
+int kd_gemv_gather_supported(int N_full, int K);
+int kd_gemv_gather(const void* x, const void* W, int64_t ldw, const int32_t* ids, int A, void* y, int N_full, int K,
+                   void* stream);
+int kd_gemv_batch_gather(const void* x, int64_t ldx, int nb, const void* W, int64_t ldw, const int32_t* ids, int A,
+                         void* y, int N_full, int K, void* stream);
+int kd_gen_select_ids(const void* scores, int64_t ld_scores, const int32_t* ids, int A, int64_t* seq, int smax,
+                      int nb, int32_t* cur_dev, float repetition_penalty, int no_repeat_ngram, int64_t* out,
+                      void* stream);
+
 /* --------------------------------------------------------- model runtime ---- */
 /* One LLaVA-OneVision instance (SigLIP -> projector -> anyres pack -> Qwen2 -> lm_head)
  * whose forward and backward layer loops run in the library (SURVEY §8b "teacher forward"

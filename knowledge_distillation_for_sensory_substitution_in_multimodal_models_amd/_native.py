@@ -130,6 +130,7 @@ _vp, _i32, _i64, _sz, _f32 = C.c_void_p, C.c_int, C.c_int64, C.c_size_t, C.c_flo
 # name -> (restype, argtypes).  Kept in the same order as include/kdstep.h.
 KD_GEMV_ROWS_MAX = 1024   # include/kdstep.h: rows per kd_gemv_rows / kd_attn_extend call
 KD_GEN_EOS_MAX = 8        # include/kdstep.h: EOS ids per kd_gen_finish call
+KD_GEN_ALLOWED_MAX = 16384   # include/kdstep.h: allowed ids per kd_gen_select_ids call
 
 SIGNATURES = {
     "kd_abi_version": (_i32, []),
@@ -195,6 +196,10 @@ SIGNATURES = {
     "kd_attn_extend_workspace_size": (_sz, [_i32, _i32, _i32, _i32]),
     "kd_attn_extend": (_i32, [_vp, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _vp, _vp, _vp,
                               _sz, _vp]),
+    "kd_gemv_gather_supported": (_i32, [_i32, _i32]),
+    "kd_gemv_gather": (_i32, [_vp, _vp, _i64, _vp, _i32, _vp, _i32, _i32, _vp]),
+    "kd_gemv_batch_gather": (_i32, [_vp, _i64, _i32, _vp, _i64, _vp, _i32, _vp, _i32, _i32, _vp]),
+    "kd_gen_select_ids": (_i32, [_vp, _i64, _vp, _i32, _vp, _i32, _i32, _vp, _f32, _i32, _vp, _vp]),
     "kd_image_resize_u8": (_i32, [_vp, _i32, _i32, _vp, _i32, _i32, _vp, _sz, _vp]),
     "kd_anyres_tiles": (_i32, [_vp, _vp, _i32, _i32, _i32, _i32, _i32, _i32, _vp, _vp, _i32, _vp]),
     "kd_anyres_batch_map": (_i32, [_vp, _i32, _i32, _vp, _i32, _vp]),

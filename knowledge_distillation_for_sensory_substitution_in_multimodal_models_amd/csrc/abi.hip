@@ -194,6 +194,19 @@ int kd_attn_extend(const void* q, const void* kn, const void* vn, void* kc, void
                    size_t wsb, void* s) {
     return kd::launch_attn_extend(q, kn, vn, kc, vc, o, nb, rows, H, HKV, hd, hdp, smax, row_start, base, ws, wsb, s);
 }
+int kd_gemv_gather_supported(int N_full, int K) { return kd::gemv_gather_ok(N_full, K) ? 1 : 0; }
+int kd_gemv_gather(const void* x, const void* W, int64_t ldw, const int32_t* ids, int A, void* y, int N_full, int K,
+                   void* s) {
+    return kd::launch_gemv_gather(x, W, ldw, ids, A, y, N_full, K, s);
+}
+int kd_gemv_batch_gather(const void* x, int64_t ldx, int nb, const void* W, int64_t ldw, const int32_t* ids, int A,
+                         void* y, int N_full, int K, void* s) {
+    return kd::launch_gemv_batch_gather(x, ldx, nb, W, ldw, ids, A, y, N_full, K, s);
+}
+int kd_gen_select_ids(const void* scores, int64_t lds, const int32_t* ids, int A, int64_t* seq, int smax, int nb,
+                      int32_t* cur, float penalty, int ngram, int64_t* out, void* s) {
+    return kd::launch_gen_select_ids(scores, lds, ids, A, seq, smax, nb, cur, penalty, ngram, out, s);
+}
 size_t kd_image_resize_workspace_size(int H, int W, int oh, int ow) { return kd::image_resize_ws(H, W, oh, ow); }
 int kd_image_resize_u8(const uint8_t* in, int H, int W, uint8_t* out, int oh, int ow, void* ws, size_t ws_bytes,
                        void* s) {

@@ -16,7 +16,10 @@
 // device, batch-invariant): k_gemv_batch (bf16 MFMA, the batch as M), k_attn_decode_part_batch,
 // k_gen_select_batch, k_rope_rows; and for generate_grouped() (one image prefill shared by its
 // questions) the suffix rows of a chunk: k_gemv_slabs (k_gemv_batch for more than 16 rows, row for
-// row the same bits) and k_attn_extend_part (ragged suffix queries against prefix + own suffix).
+// row the same bits) and k_attn_extend_part (ragged suffix queries against prefix + own suffix);
+// and for an allowed set of token ids (the evaluation's RestrictedLogitsProcessor,
+// evaluate_onevision.py:141-158) k_gemv_gather / k_gemv_batch_gather (the lm_head over the allowed
+// rows only, with the full head's bits) and k_gen_select_ids (the choice among the allowed ids).
 //
 // Each algorithm has one body.  The single-row and the batched form of a kernel differ in where a
 // row's pointers and length come from, not in what is computed, so they share a __forceinline__
@@ -185,7 +188,8 @@ __device__ __forceinline__ void stage_x(const bf16* __restrict__ x, const bf16* 
 // With the two behind one __forceinline__ body (k stride and reduction as parameters) hipcc
 // schedules the loop differently (same registers, same occupancy, same bits), and these 5 - 9 us
 // kernels, ~100 launches per token, came out 3 - 7 % slower in a kernel trace: generate() lost
-// 0.8 ms of 48 (profiles/decode_dedupe/bench_ab.txt).  A change to one loop belongs in the other.
+// 0.8 ms of 48 (profiles/decode_dedupe/bench_ab.txt).  A change to one loop belongs in the other,
+// and a change to k_gemv's in k_gemv_gather, whose logits must stay k_gemv's bit for bit.
 template <int EPI>
 __global__ void __launch_bounds__(NT) k_gemv(const bf16* __restrict__ x, const bf16* __restrict__ W, int64_t ldw,
                                              const bf16* __restrict__ extra, bf16* __restrict__ y, int N, int K,
@@ -930,6 +934,173 @@ __global__ void __launch_bounds__(NT) k_attn_extend_part(const bf16* __restrict_
     }
 }
 
+// ------------------------------------- constrained decoding: an allowed set of token ids ----
+// With allowed_token_ids the step needs the logits of the A allowed ids only (ids: ascending,
+// unique int32 on the device), so the lm_head reads A weight rows instead of V and the choice
+// searches A scores.  The gathered GEMVs are kernels of their own, not an index pointer threaded
+// through k_gemv / k_gemv_batch (see k_gemv: an edit there reschedules its loop).  They repeat the
+// full kernels' arithmetic on a row: in k_gemv a logit is one wave's sum over its own weight row,
+// in k_gemv_batch under the lm_head plan (wave_n = 1, ksplit = 1) one whole-K MFMA chain whose
+// column n reads weight row n only, so y[., j] has the bits the full head gives at column ids[j].
+// An id outside [0, N_full) reads no weight and scores -inf.
+
+// k_gemv (EPI 0, no norm) over weight rows ids[0 .. A): its dot-product loop, a third copy.
+__global__ void __launch_bounds__(NT) k_gemv_gather(const bf16* __restrict__ x, const bf16* __restrict__ W, int64_t ldw,
+                                                    const int* __restrict__ ids, int A, bf16* __restrict__ y,
+                                                    int N_full, int K) {
+    extern __shared__ float xs[];
+    __shared__ float red[8];
+    stage_x(x, nullptr, 0.f, K, xs, red);
+    const int j = blockIdx.x * (NT / 64) + (threadIdx.x >> 6), lane = threadIdx.x & 63;
+    if (j >= A) return;
+    const int n = ids[j];
+    if ((unsigned)n >= (unsigned)N_full) {
+        if (lane == 0) y[j] = (bf16)(-INFINITY);
+        return;
+    }
+    const bf16* r0 = W + (size_t)n * ldw;
+    float a0 = 0.f;
+    for (int k = lane * 8; k < K; k += 512) {
+        const bf16x8 w0 = *(const bf16x8*)(r0 + k);
+#pragma unroll
+        for (int e = 0; e < 8; ++e) a0 += xs[k + e] * (float)w0[e];
+    }
+    a0 = wave_sum(a0);
+    if (lane == 0) y[j] = (bf16)a0;
+}
+
+// k_gemv_batch's wave_n = 1, ksplit = 1 plan (EPI 0, no norm) over 16-row tiles of the gathered
+// rows: tile t of wave (blockIdx.x, w) holds weight rows ids[16 t .. 16 t + 16), y is [nb, A].
+// Same slab staging (gb_stage_slab), same ascending 32-k chain per wave, so batch invariant as
+// k_gemv_batch is.
+__global__ void __launch_bounds__(NT) k_gemv_batch_gather(const bf16* __restrict__ x, int64_t ldx,
+                                                          const bf16* __restrict__ W, int64_t ldw,
+                                                          const int* __restrict__ ids, int A, bf16* __restrict__ y,
+                                                          int nb, int N_full, int K) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char gb_smem[];
+    __shared__ float rstd_s[GB_ROWS];   // gb_stage_slab's norm scratch: not touched without norm_w
+    bf16* xs = (bf16*)gb_smem;
+    const int w = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    const int ksteps = (K + 31) >> 5, XLD = ksteps * 32 + GB_PAD;
+    const bf16x8 zero8 = {};
+    const int tile = blockIdx.x * (NT / 64) + w;
+    const int col = lane & 15, kq = (lane >> 4) * 8;
+    const int j = tile * 16 + col, id = ids[min(j, A - 1)];   // entries past A: a valid entry is read, nothing stored
+    const bool id_ok = (unsigned)id < (unsigned)N_full;
+    const bf16* r0 = W + (size_t)(id_ok ? id : 0) * ldw;
+    // k_gemv_batch's loop: the first GB_PF fragments in flight while x is staged, then the rest; loads
+    // past the K tail stay unconditional, on the row's first chunk, and are replaced by zeros.  (All
+    // ksteps fragments loaded up front, 236 VGPRs, measured the same 14 us per launch at A = 500.)
+    bf16x8 pf0[GB_PF];
+#pragma unroll
+    for (int i = 0; i < GB_PF; ++i) {
+        const int k = i * 32 + kq;
+        const bool in = i < ksteps && k < K;
+        pf0[i] = *(const bf16x8*)(r0 + (in ? k : 0));
+    }
+    gb_stage_slab(x, ldx, nb, K, 0, ksteps, nullptr, 0.f, rstd_s, xs);
+    const bf16* xr = xs + col * XLD + kq;
+    f32x4 acc0 = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+    for (int i = 0; i < GB_PF; ++i) {
+        if (i < ksteps) {   // uniform
+            const bool in = i * 32 + kq < K;
+            const bf16x8 a = *(const bf16x8*)(xr + i * 32);
+            acc0 = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, in ? pf0[i] : zero8, acc0, 0, 0, 0);
+        }
+    }
+#pragma unroll 4
+    for (int s = GB_PF; s < ksteps; ++s) {
+        const int k = s * 32 + kq;
+        const bool in = k < K;
+        const bf16x8 a = *(const bf16x8*)(xr + s * 32);
+        const bf16x8 l0 = *(const bf16x8*)(r0 + (in ? k : 0));
+        acc0 = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, in ? l0 : zero8, acc0, 0, 0, 0);
+    }
+    if (j >= A) return;
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+        const int b = (lane >> 4) * 4 + r;
+        if (b < nb) y[(size_t)b * A + j] = id_ok ? (bf16)acc0[r] : (bf16)(-INFINITY);
+    }
+}
+
+// Entry of the ascending ids[0 .. A) that equals t, or -1.  (Searching a copy of the ids in LDS
+// took the kernel from 9.5 to 7.8 us at A = 500, 16 rows: not worth a second path.)
+__device__ __forceinline__ int ids_find(const int* __restrict__ ids, int A, int64_t t) {
+    int lo = 0, hi = A;   // the first entry >= t lies in [lo, hi]
+    while (lo < hi) {
+        const int mid = (lo + hi) >> 1;
+        if ((int64_t)ids[mid] < t) lo = mid + 1;
+        else hi = mid;
+    }
+    return lo < A && (int64_t)ids[lo] == t ? lo : -1;
+}
+
+// k_gen_select_batch over compact scores [nb, A] (column j: token ids[j]): row b = blockIdx.x.  The
+// flags (bit 0 = seen, bit 1 = banned) are kept per allowed entry in LDS, and every id of the
+// sequence is looked up in ids by binary search (a miss touches nothing), so the cost follows A
+// and the row's length, never V.  Ascending ids: the lowest entry on a tie is the lowest id.  No
+// finite allowed score: token 0, as the argmax of an all -inf row of V logits.
+__global__ void __launch_bounds__(1024) k_gen_select_ids(const bf16* __restrict__ scores_all, int64_t lds,
+                                                         const int* __restrict__ ids, int A,
+                                                         int64_t* __restrict__ seq_all, int smax,
+                                                         int* __restrict__ cur_dev, float penalty, int ngram,
+                                                         int64_t* __restrict__ out) {
+    __shared__ uint8_t flags[KD_GEN_ALLOWED_MAX];
+    __shared__ float sv[16];
+    __shared__ int si[16];
+    const int b = blockIdx.x;
+    int64_t* seq = seq_all + (size_t)b * smax;
+    const bf16* scores = scores_all + (size_t)b * lds;
+    const int len = max(0, min(cur_dev[b], smax));   // the ids read never leave the row
+    for (int i = threadIdx.x; i < A; i += blockDim.x) flags[i] = 0;
+    __syncthreads();
+    if (penalty != 1.0f)
+        for (int i = threadIdx.x; i < len; i += blockDim.x) {
+            const int j = ids_find(ids, A, seq[i]);
+            if (j >= 0) flags[j] = 1;
+        }
+    __syncthreads();   // the two processors set different bits of the same bytes
+    if (ngram > 0 && len + 1 >= ngram)
+        for (int i = threadIdx.x; i + ngram <= len; i += blockDim.x) {
+            bool match = true;
+            for (int k = 0; k < ngram - 1; ++k) match &= seq[i + k] == seq[len - ngram + 1 + k];
+            if (match) {
+                const int j = ids_find(ids, A, seq[i + ngram - 1]);
+                if (j >= 0) flags[j] |= 2;
+            }
+        }
+    __syncthreads();
+    float best = -INFINITY;
+    int bj = 0x7fffffff;
+    for (int j = threadIdx.x; j < A; j += blockDim.x) {
+        float s = (float)scores[j];
+        const uint32_t f = flags[j];
+        if (f & 1) s = s < 0.f ? __fmul_rn(s, penalty) : __fdiv_rn(s, penalty);
+        if (f & 2) s = -INFINITY;
+        if (s > best || (s == best && j < bj)) { best = s; bj = j; }   // NaN never wins
+    }
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) {
+        const float ov = __shfl_xor(best, off, 64);
+        const int oj = __shfl_xor(bj, off, 64);
+        if (ov > best || (ov == best && oj < bj)) { best = ov; bj = oj; }
+    }
+    const int w = threadIdx.x >> 6;
+    if ((threadIdx.x & 63) == 0) { sv[w] = best; si[w] = bj; }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        for (int k = 1; k < (int)(blockDim.x >> 6); ++k)
+            if (sv[k] > best || (sv[k] == best && si[k] < bj)) { best = sv[k]; bj = si[k]; }
+        // best == -inf: every allowed entry is banned, -inf or NaN (bj is then entry 0 or none at all)
+        const int64_t tok = best == -INFINITY ? 0 : (int64_t)ids[bj];
+        if (len < smax) seq[len] = tok;
+        if (out) out[b] = tok;
+        cur_dev[b] = len + 1;
+    }
+}
+
 }  // namespace
 
 // Launch plan of k_gemv_batch: a function of (N, K) alone.  Never of nb.
@@ -1245,6 +1416,63 @@ int launch_gen_select(const void* logits, int V, int64_t* seq, int len, int* cur
     hipLaunchKernelGGL(k_gen_select, dim3(1), dim3(1024), 0, as_stream(stream), (const bf16*)logits, V, seq, len,
                        cur_dev, penalty, ngram, (uint8_t*)flags_ws, out);
     KD_LAUNCH_CHECK("k_gen_select");
+    return KD_OK;
+}
+
+// Where a gathered logit has the full head's bits: the full-vocabulary routes whose per-row order
+// does not depend on N.  kd_gemv: the wave-per-row k_gemv, not k_gemv_wide; kd_gemv_batch: one
+// whole-K chain per tile (wave_n = 1, ksplit = 1).  The second implies the first (>= 2048 tiles),
+// and both gathered entries take the one set.
+bool gemv_gather_ok(int N_full, int K) {
+    if (N_full <= 0 || K <= 0 || K % 8 != 0 || K > 16384) return false;
+    const GemvBatchPlan p = gemv_batch_plan(N_full, K);
+    const bool wide = N_full < 4096 && K >= 512;
+    return !wide && p.wave_n == 1 && p.ksplit == 1;
+}
+
+// The checks the two gathered GEMVs share (x rows: check_gemv_args' rule for the entry).
+static int check_gather_args(const char* who, const void* ids, int A, int N_full, int K) {
+    auto msg = [who](const char* what) { return std::string(who) + ": " + what; };
+    KD_CHECK_ARG(ids, msg("null pointer"));
+    KD_CHECK_SHAPE(A >= 1 && A <= N_full, msg("1 <= A <= N_full"));
+    KD_CHECK_SHAPE(gemv_gather_ok(N_full, K), msg("(N_full, K) outside kd_gemv_gather_supported"));
+    return KD_OK;
+}
+
+int launch_gemv_gather(const void* x, const void* W, int64_t ldw, const int* ids, int A, void* y, int N_full, int K,
+                       void* stream) {
+    if (int rc = check_gemv_args("gemv_gather", x, 0, 1, 1, nullptr, W, ldw, nullptr, y, N_full, K, 0, 0, nullptr))
+        return rc;
+    if (int rc = check_gather_args("gemv_gather", ids, A, N_full, K)) return rc;
+    hipLaunchKernelGGL(k_gemv_gather, dim3((A + NT / 64 - 1) / (NT / 64)), dim3(NT), (size_t)K * sizeof(float),
+                       as_stream(stream), (const bf16*)x, (const bf16*)W, ldw, ids, A, (bf16*)y, N_full, K);
+    KD_LAUNCH_CHECK("k_gemv_gather");
+    return KD_OK;
+}
+
+int launch_gemv_batch_gather(const void* x, int64_t ldx, int nb, const void* W, int64_t ldw, const int* ids, int A,
+                             void* y, int N_full, int K, void* stream) {
+    if (int rc = check_gemv_args("gemv_batch_gather", x, ldx, nb, GB_ROWS, "1 <= nb <= 16", W, ldw, nullptr, y, N_full, K,
+                                 0, 0, nullptr))
+        return rc;
+    if (int rc = check_gather_args("gemv_batch_gather", ids, A, N_full, K)) return rc;
+    const int tiles = (A + 15) / 16, ksteps = (K + 31) / 32;   // ksteps <= GB_MAX_STEPS: ksplit = 1
+    const size_t lds = (size_t)GB_ROWS * (ksteps * 32 + GB_PAD) * sizeof(bf16);
+    hipLaunchKernelGGL(k_gemv_batch_gather, dim3((tiles + NT / 64 - 1) / (NT / 64)), dim3(NT), lds, as_stream(stream),
+                       (const bf16*)x, ldx, (const bf16*)W, ldw, ids, A, (bf16*)y, nb, N_full, K);
+    KD_LAUNCH_CHECK("k_gemv_batch_gather");
+    return KD_OK;
+}
+
+int launch_gen_select_ids(const void* scores, int64_t lds, const int* ids, int A, int64_t* seq, int smax, int nb,
+                          int* cur_dev, float penalty, int ngram, int64_t* out, void* stream) {
+    KD_CHECK_ARG(scores && ids && seq && cur_dev, "gen_select_ids: null pointer");
+    KD_CHECK_SHAPE(A >= 1 && A <= KD_GEN_ALLOWED_MAX && smax > 0 && lds >= A && nb >= 1 && nb <= GB_ROWS,
+                   "gen_select_ids: 1 <= A <= KD_GEN_ALLOWED_MAX, smax positive, ld >= A, 1 <= nb <= 16");
+    KD_CHECK_ARG(penalty > 0.f && ngram >= 0, "gen_select_ids: penalty must be > 0 and ngram >= 0");
+    hipLaunchKernelGGL(k_gen_select_ids, dim3(nb), dim3(1024), 0, as_stream(stream), (const bf16*)scores, lds, ids, A, seq,
+                       smax, cur_dev, penalty, ngram, out);
+    KD_LAUNCH_CHECK("k_gen_select_ids");
     return KD_OK;
 }
 

@@ -95,6 +95,13 @@ size_t attn_extend_ws(int rows, int H, int hd, int smax);
 int launch_attn_extend(const void* q, const void* k_new, const void* v_new, void* kc, void* vc, void* o, int nb,
                        int rows, int H, int HKV, int hd, int hdp, int smax, const int* row_start, const int* base,
                        void* ws, size_t ws_bytes, void* stream);
+bool gemv_gather_ok(int N_full, int K);
+int launch_gemv_gather(const void* x, const void* W, int64_t ldw, const int* ids, int A, void* y, int N_full, int K,
+                       void* stream);
+int launch_gemv_batch_gather(const void* x, int64_t ldx, int nb, const void* W, int64_t ldw, const int* ids, int A,
+                             void* y, int N_full, int K, void* stream);
+int launch_gen_select_ids(const void* scores, int64_t lds, const int* ids, int A, int64_t* seq, int smax, int nb,
+                          int* cur_dev, float penalty, int ngram, int64_t* out, void* stream);
 int launch_image_resize(const uint8_t* in, int H, int W, uint8_t* out, int oh, int ow, void* ws, size_t ws_bytes,
                         void* stream);
 int launch_anyres_tiles(const uint8_t* base, const uint8_t* resized, int nh, int nw, int bh, int bw, int patch,

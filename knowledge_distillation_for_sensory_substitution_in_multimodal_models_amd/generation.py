@@ -33,13 +33,36 @@ weights again per 16 rows; kd_attn_extend: suffix queries against prefix + own s
 batched decode of generate_batch() takes over.  A question's result depends on its image, the
 shared prefix and its own suffix only (bit for bit); it is held to generate_batch()'s oracle
 bounds but is not bit-identical to generate_batch() on the same prompt.
+
+Constrained decoding.  The evaluation restricts the choice to the tokens of its answers table
+(evaluate_onevision.py:141-158: a user logits processor that adds 0 to the allowed ids and -inf to
+every other id, which transformers runs behind its own processors).  All three entry points take
+that set as allowed_token_ids (any int sequence or int tensor; allowed_ids() sorts and deduplicates
+it once, before the graph capture, and raises ValueError for an empty set, an id outside
+[0, vocab) or more than KD_GEN_ALLOWED_MAX ids, before any device work); None is the unrestricted
+call, launch for launch.  With a set:
+  - the mask comes after the repetition penalty and the no-repeat-n-gram ban; the token is the
+    allowed id with the largest processed fp32 score, the lowest id on a tie, never a NaN;
+  - the penalty applies to an allowed id that occurs in the sequence (prompt or generated); ids of
+    the sequence that are not allowed matter as n-gram context only;
+  - if every allowed id is banned (or -inf / NaN) the token is 0, allowed or not: the argmax of an
+    all -inf row, the unrestricted kernels' rule;
+  - a row ends only if an EOS id is in the set and is chosen; otherwise it runs max_new_tokens;
+  - return_logits gives compact bf16 rows [1, A]: column j is the logit of the j-th smallest allowed
+    id (the order of allowed_ids()), bit-identical to the full row's element at that id.
+The prefill's token comes from the full logits row's allowed columns (generate_grouped(): from the
+gathered head behind its extend pass).  A decode step reads only the A allowed rows of the lm_head
+(kd_gemv_gather / kd_gemv_batch_gather) and searches A scores (kd_gen_select_ids: flags per allowed
+entry, sequence tokens found by binary search) where ops.gemv_gather_supported(vocab, hidden) holds;
+elsewhere, or with restrict_head=False, it runs the full head and takes the allowed columns: the
+same bits either way.  restrict_head=True raises ValueError where the gathered head does not exist.
 """
 from __future__ import annotations
 
 import torch
 
 from . import ops
-from ._native import KD_GEMV_ROWS_MAX, KD_GEN_EOS_MAX
+from ._native import KD_GEMV_ROWS_MAX, KD_GEN_ALLOWED_MAX, KD_GEN_EOS_MAX
 
 
 EOS_TOKEN_IDS = (151645,)   # <|im_end|>: generation_config.eos_token_id of the -ov-hf chat checkpoints
@@ -120,6 +143,64 @@ def _eos_set(eos_token_id) -> set:
     return {int(e) for e in ([eos_token_id] if isinstance(eos_token_id, int) else (eos_token_id or ()))}
 
 
+def allowed_ids(allowed_token_ids, vocab: int) -> torch.Tensor:
+    """allowed_token_ids (any sequence of ints or an integer tensor, any order, repeats welcome) as
+    the kernels take them: a sorted, unique int32 tensor on the host.  ValueError for an empty set,
+    an id outside [0, vocab), more than KD_GEN_ALLOWED_MAX distinct ids or anything but integers.
+    Touches no device."""
+    t = allowed_token_ids.detach().cpu() if isinstance(allowed_token_ids, torch.Tensor) \
+        else torch.tensor(list(allowed_token_ids))
+    if t.numel() == 0:
+        raise ValueError("allowed_token_ids: the set is empty")
+    if t.dtype.is_floating_point or t.dtype.is_complex or t.dtype == torch.bool:
+        raise ValueError(f"allowed_token_ids: integer ids expected, got {t.dtype}")
+    t = torch.unique(t.reshape(-1).to(torch.int64))   # sorted ascending
+    if int(t[0]) < 0 or int(t[-1]) >= int(vocab):
+        raise ValueError(f"allowed_token_ids: every id must lie in [0, {int(vocab)})")
+    if t.numel() > KD_GEN_ALLOWED_MAX:
+        raise ValueError(f"allowed_token_ids: more than {KD_GEN_ALLOWED_MAX} ids")
+    return t.to(torch.int32)
+
+
+class _Allowed:
+    """The allowed set of one call, normalised once (before the graph capture: the step's arguments
+    stay fixed): ids ascending on the device, and which head the decode step takes.  gather: only the
+    allowed rows of the lm_head are read (kd_gemv_gather / kd_gemv_batch_gather); else the full head
+    runs and its allowed columns are taken.  Both give the same bits."""
+
+    def __init__(self, model, allowed_token_ids, restrict_head, who: str):
+        T = model.cfg.text
+        host = allowed_ids(allowed_token_ids, T.vocab)
+        supported = ops.gemv_gather_supported(T.vocab, T.hidden)
+        if restrict_head and not supported:
+            raise ValueError(f"{who}: restrict_head=True, but the gathered head does not exist for a "
+                             f"[{T.vocab}, {T.hidden}] lm_head (ops.gemv_gather_supported)")
+        self.gather = supported if restrict_head is None else bool(restrict_head)
+        self.ids = host.to(model.device)
+        self.cols = self.ids.long()
+
+    def columns(self, logits):
+        """Full logits [nb, V] -> their allowed columns [nb, A], ascending ids."""
+        return logits.index_select(1, self.cols)
+
+    def head(self, hn, w, batch: bool):
+        """The allowed logits [nb, A] of the final-norm rows hn."""
+        if self.gather:
+            return (ops.gemv_batch_gather if batch else ops.gemv_gather)(hn, w, self.ids)
+        return self.columns((ops.gemv_batch if batch else ops.gemv)(hn, w))
+
+    def select(self, scores, seq, cur, repetition_penalty, no_repeat_ngram_size, out=None):
+        ops.gen_select_ids(scores, self.ids, seq, cur, repetition_penalty, no_repeat_ngram_size, out=out)
+
+
+def _allowed(model, allowed_token_ids, restrict_head, who: str):
+    if allowed_token_ids is None:
+        if restrict_head is not None:
+            raise ValueError(f"{who}: restrict_head is about allowed_token_ids, which is None")
+        return None
+    return _Allowed(model, allowed_token_ids, restrict_head, who)
+
+
 def _decode_layers(model):
     """Per layer: (input norm, q|k|v weight, q|k|v bias, o_proj, post-attention norm, gate|up, down)."""
     T, P = model.cfg.text, model.P
@@ -183,7 +264,7 @@ def generate(model, input_ids: torch.Tensor, pixel_values: torch.Tensor, image_s
              repetition_penalty: float = 1.0, no_repeat_ngram_size: int = 0, eos_token_id=EOS_TOKEN_IDS,
              pad_token_id: int | None = None, temperature: float | None = None, return_logits: bool = False,
              graph: bool = True, fuse_norm: bool | None = None, stop_check_every: int | None = None,
-             stats: dict | None = None):
+             stats: dict | None = None, allowed_token_ids=None, restrict_head: bool | None = None):
     """-> int64 [1, L + n_new] on the device (and the bf16 logits row of every step if
     return_logits).  `temperature` is accepted for signature parity and ignored (greedy).
     fuse_norm: RMSNorm fused into the q|k|v and gate|up GEMVs (default: FUSE_NORM_DEFAULT).
@@ -192,9 +273,12 @@ def generate(model, input_ids: torch.Tensor, pixel_values: torch.Tensor, image_s
     min(n, k * max(1, ceil(s / k))) of its n = max_new_tokens - 1 steps (s: the step that produced the
     EOS, 0 for the prefill's token, n if none).  The result is the same bits for every k.
     stats (a dict) receives one-entry lists steps_run, steps_max, checks (host reads) and finished_at
-    ([length at the first EOS, or 0])."""
+    ([length at the first EOS, or 0]).
+    allowed_token_ids, restrict_head: constrained decoding, see the module docstring (the logits
+    returned are then the compact rows [1, A])."""
     del temperature, pad_token_id   # greedy, batch of one: no padding of finished rows
     k_stop = _stop_every(stop_check_every, "generate")
+    allowed = _allowed(model, allowed_token_ids, restrict_head, "generate")
     _stats_begin(stats)
     FUSE_NORM = FUSE_NORM_DEFAULT if fuse_norm is None else bool(fuse_norm)
     if input_ids.dim() != 2 or input_ids.shape[0] != 1:
@@ -220,8 +304,13 @@ def generate(model, input_ids: torch.Tensor, pixel_values: torch.Tensor, image_s
     seq[:L].copy_(input_ids[0])
     logits = model.logits(fwd["hn"][L - 1:L])
     del fwd
+    if allowed is None:
+        ops.gen_select(logits, seq, L, repetition_penalty, no_repeat_ngram_size)
+    else:
+        logits = allowed.columns(logits)
+        allowed.select(logits, seq.view(1, smax), torch.full((1,), L, dtype=torch.int32, device=dev),
+                       repetition_penalty, no_repeat_ngram_size)
     steps = [logits] if return_logits else None
-    ops.gen_select(logits, seq, L, repetition_penalty, no_repeat_ngram_size)
 
     cos, sin = model._rope_for(smax)
     src = torch.full((1,), -2, dtype=torch.int32, device=dev)   # token embedding (kd_embed_assemble)
@@ -258,8 +347,12 @@ def generate(model, input_ids: torch.Tensor, pixel_values: torch.Tensor, image_s
         # final norm as its own launch: fused into the 38k-workgroup lm_head GEMV it would be recomputed
         # by every workgroup (measured slower)
         hn, _, _ = ops.norm_fwd(x, P[lp + "norm.weight"], None, T.eps, rms=True, save_stats=False)
-        lg = ops.gemv(hn, model.lm_head_weight())
-        ops.gen_select(lg, seq, 0, repetition_penalty, no_repeat_ngram_size, out=tok, cur=cur)
+        if allowed is None:
+            lg = ops.gemv(hn, model.lm_head_weight())
+            ops.gen_select(lg, seq, 0, repetition_penalty, no_repeat_ngram_size, out=tok, cur=cur)
+        else:
+            lg = allowed.head(hn, model.lm_head_weight(), batch=False)
+            allowed.select(lg, seq.view(1, smax), cur, repetition_penalty, no_repeat_ngram_size, out=tok)
         stop.mark(tok, cur)
         return lg
 
@@ -281,7 +374,8 @@ MAX_BATCH = 16   # rows per decode step: the M dimension of the MFMA behind kd_g
 def generate_batch(model, prompts, max_new_tokens: int = 32, repetition_penalty: float = 1.0,
                    no_repeat_ngram_size: int = 0, eos_token_id=EOS_TOKEN_IDS, pad_token_id: int | None = None,
                    temperature: float | None = None, return_logits: bool = False, graph: bool = True,
-                   stop_check_every: int | None = None, stats: dict | None = None):
+                   stop_check_every: int | None = None, stats: dict | None = None, allowed_token_ids=None,
+                   restrict_head: bool | None = None):
     """generate() for several prompts at once: prompts is a sequence of (input_ids [1, L_i],
     pixel_values [1, P_i, 3, 384, 384], image_sizes [1, 2]), ragged in L_i and P_i (no padding, no
     attention mask) -> list of int64 [1, L_i + n_i] (and, with return_logits, a list per row of the
@@ -297,9 +391,11 @@ def generate_batch(model, prompts, max_new_tokens: int = 32, repetition_penalty:
     asks the device every stop_check_every = k steps (generate(): s is then the step that produced
     the last row's first EOS), so the results are the same bits for every k.  stats (a dict)
     receives, per chunk, steps_run, steps_max, checks and finished_at (per row the length at its
-    first EOS, or 0)."""
+    first EOS, or 0).  allowed_token_ids, restrict_head: constrained decoding, see the module
+    docstring (the logits returned are then the compact rows [1, A])."""
     del temperature, pad_token_id   # greedy; finished rows are cut, not padded
     k_stop = _stop_every(stop_check_every, "generate_batch")
+    allowed = _allowed(model, allowed_token_ids, restrict_head, "generate_batch")
     _stats_begin(stats)
     prompts = list(prompts)
     if not prompts:
@@ -312,14 +408,14 @@ def generate_batch(model, prompts, max_new_tokens: int = 32, repetition_penalty:
     outs, logs = [], []
     for c0 in range(0, len(prompts), MAX_BATCH):
         o, lg = _generate_rows(model, prompts[c0:c0 + MAX_BATCH], int(max_new_tokens), repetition_penalty,
-                               no_repeat_ngram_size, eos_token_id, return_logits, graph, k_stop, stats)
+                               no_repeat_ngram_size, eos_token_id, return_logits, graph, k_stop, stats, allowed)
         outs += o
         logs += lg
     return (outs, logs) if return_logits else outs
 
 
 def _generate_rows(model, prompts, max_new_tokens, repetition_penalty, no_repeat_ngram_size, eos_token_id,
-                   return_logits, graph, k_stop, stats):
+                   return_logits, graph, k_stop, stats, allowed):
     T = model.cfg.text
     dev = model.device
     nb = len(prompts)
@@ -344,16 +440,21 @@ def _generate_rows(model, prompts, max_new_tokens, repetition_penalty, no_repeat
         seq[b, :L].copy_(input_ids[0])
         logits = model.logits(fwd["hn"][L - 1:L])
         del fwd
+        if allowed is None:
+            ops.gen_select(logits, seq[b], L, repetition_penalty, no_repeat_ngram_size)
+        else:
+            logits = allowed.columns(logits)
+            allowed.select(logits, seq[b:b + 1], torch.full((1,), L, dtype=torch.int32, device=dev),
+                           repetition_penalty, no_repeat_ngram_size)
         if return_logits:
             steps[b].append(logits)
-        ops.gen_select(logits, seq[b], L, repetition_penalty, no_repeat_ngram_size)
 
     return _decode_rows(model, kc, vc, seq, Ls, steps, max_new_tokens, repetition_penalty, no_repeat_ngram_size, eos,
-                        return_logits, graph, k_stop, stats)
+                        return_logits, graph, k_stop, stats, allowed)
 
 
 def _decode_rows(model, kc, vc, seq, Ls, steps, max_new_tokens, repetition_penalty, no_repeat_ngram_size, eos,
-                 return_logits, graph, k_stop, stats):
+                 return_logits, graph, k_stop, stats, allowed=None):
     """The batched decode loop behind generate_batch() and generate_grouped(): row b's caches hold
     its L_b prompt positions, seq[b, L_b] its first new token and steps[b] that token's logits row.
     The loop ends early once every row has emitted an EOS (_Stop)."""
@@ -385,8 +486,12 @@ def _decode_rows(model, kc, vc, seq, Ls, steps, max_new_tokens, repetition_penal
             a = ops.gemv_batch(x_mid, Wgu, swiglu_inter=T.inter, norm_w=w_post, eps=T.eps)  # post_attention_layernorm
             x = ops.gemv_batch(a, Wdown, residual=x_mid)
         hn, _, _ = ops.norm_fwd(x, P[lp + "norm.weight"], None, T.eps, rms=True, save_stats=False)
-        lg = ops.gemv_batch(hn, model.lm_head_weight())
-        ops.gen_select_batch(lg, seq, cur, repetition_penalty, no_repeat_ngram_size, out=tok)
+        if allowed is None:
+            lg = ops.gemv_batch(hn, model.lm_head_weight())
+            ops.gen_select_batch(lg, seq, cur, repetition_penalty, no_repeat_ngram_size, out=tok)
+        else:
+            lg = allowed.head(hn, model.lm_head_weight(), batch=True)
+            allowed.select(lg, seq, cur, repetition_penalty, no_repeat_ngram_size, out=tok)
         stop.mark(tok, cur)
         return lg
 
@@ -411,7 +516,8 @@ def _decode_rows(model, kc, vc, seq, Ls, steps, max_new_tokens, repetition_penal
 def generate_grouped(model, groups, max_new_tokens: int = 32, repetition_penalty: float = 1.0,
                      no_repeat_ngram_size: int = 0, eos_token_id=EOS_TOKEN_IDS, pad_token_id: int | None = None,
                      temperature: float | None = None, return_logits: bool = False, graph: bool = True,
-                     stop_check_every: int | None = None, stats: dict | None = None):
+                     stop_check_every: int | None = None, stats: dict | None = None, allowed_token_ids=None,
+                     restrict_head: bool | None = None):
     """generate_batch() for questions grouped by image: groups is a sequence of (pixel_values
     [1, P, 3, 384, 384], image_sizes [1, 2], [input_ids [1, L_q], ...]) -> one list per group of int64
     [1, L_q + n_q] (and, with return_logits, the same nesting of per-step bf16 logits rows).
@@ -431,9 +537,12 @@ def generate_grouped(model, groups, max_new_tokens: int = 32, repetition_penalty
     against the oracle.
 
     stop_check_every and stats as in generate_batch(): a chunk of up to MAX_BATCH questions stops
-    decoding once all of them have emitted an EOS (one stats entry per chunk)."""
+    decoding once all of them have emitted an EOS (one stats entry per chunk).
+    allowed_token_ids, restrict_head: constrained decoding, see the module docstring (the logits
+    returned are then the compact rows [1, A]; the head behind the extend pass is gathered too)."""
     del temperature, pad_token_id   # greedy; finished rows are cut, not padded
     k_stop = _stop_every(stop_check_every, "generate_grouped")
+    allowed = _allowed(model, allowed_token_ids, restrict_head, "generate_grouped")
     _stats_begin(stats)
     groups = [(px, sizes, list(qs)) for px, sizes, qs in groups]
     if not groups:
@@ -468,7 +577,7 @@ def generate_grouped(model, groups, max_new_tokens: int = 32, repetition_penalty
         chunk = items[c0:c0 + MAX_BATCH]
         o, lg, carry = _generate_grouped_rows(model, chunk, carry, int(max_new_tokens), repetition_penalty,
                                               no_repeat_ngram_size, eos_token_id, return_logits, graph, k_stop,
-                                              stats)
+                                              stats, allowed)
         for (gi, *_), ob, lb in zip(chunk, o, lg if return_logits else [None] * len(o)):
             outs[gi].append(ob)
             logs[gi].append(lb)
@@ -476,7 +585,7 @@ def generate_grouped(model, groups, max_new_tokens: int = 32, repetition_penalty
 
 
 def _generate_grouped_rows(model, chunk, carry, max_new_tokens, repetition_penalty, no_repeat_ngram_size, eos_token_id,
-                           return_logits, graph, k_stop, stats):
+                           return_logits, graph, k_stop, stats, allowed):
     T, P = model.cfg.text, model.P
     dev = model.device
     nb = len(chunk)
@@ -537,10 +646,14 @@ def _generate_grouped_rows(model, chunk, carry, max_new_tokens, repetition_penal
         b0 = b1
     xl = last[0] if len(last) == 1 else torch.cat(last)
     hn, _, _ = ops.norm_fwd(xl, P[lp + "norm.weight"], None, T.eps, rms=True, save_stats=False)
-    lg = ops.gemv_batch(hn, model.lm_head_weight())
     cur = torch.tensor(Ls, dtype=torch.int32, device=dev)
-    ops.gen_select_batch(lg, seq, cur, repetition_penalty, no_repeat_ngram_size)   # seq[b, L_b]; cur = L_b + 1
+    if allowed is None:
+        lg = ops.gemv_batch(hn, model.lm_head_weight())
+        ops.gen_select_batch(lg, seq, cur, repetition_penalty, no_repeat_ngram_size)   # seq[b, L_b]; cur = L_b + 1
+    else:
+        lg = allowed.head(hn, model.lm_head_weight(), batch=True)
+        allowed.select(lg, seq, cur, repetition_penalty, no_repeat_ngram_size)
     steps = [[lg[b:b + 1]] if return_logits else [] for b in range(nb)]
     outs, steps = _decode_rows(model, kc, vc, seq, Ls, steps, max_new_tokens, repetition_penalty,
-                               no_repeat_ngram_size, eos, return_logits, graph, k_stop, stats)
+                               no_repeat_ngram_size, eos, return_logits, graph, k_stop, stats, allowed)
     return outs, steps, carry

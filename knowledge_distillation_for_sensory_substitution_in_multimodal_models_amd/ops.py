@@ -927,3 +927,74 @@ def attn_extend(q: torch.Tensor, k_new: torch.Tensor, v_new: torch.Tensor, k_cac
             v_cache.data_ptr(), out.data_ptr(), nb, rows, H, HKV, hd, hdp, smax, row_start.data_ptr(),
             base.data_ptr(), ws.data_ptr(), ws.numel(), _stream())
     return out
+
+
+# ------------------------------------------------------------ constrained decoding ----
+def gemv_gather_supported(n_full: int, k: int) -> bool:
+    """Whether gemv_gather() / gemv_batch_gather() exist for a [n_full, k] weight: where the full
+    gemv() / gemv_batch() compute a row in an order that does not depend on N, so the gathered
+    logits are theirs bit for bit (kd_gemv_gather_supported)."""
+    return bool(NV.lib().kd_gemv_gather_supported(int(n_full), int(k)))
+
+
+def _gather_ids(ids: torch.Tensor, who: str) -> int:
+    _require(ids, torch.int32, f"{who}.ids")
+    if ids.dim() != 1 or ids.numel() < 1 or not ids.is_contiguous():
+        raise RuntimeError(f"{who}: ids must be a contiguous, non-empty [A] tensor (ascending, unique)")
+    return ids.numel()
+
+
+def gemv_gather(x: torch.Tensor, w: torch.Tensor, ids: torch.Tensor) -> torch.Tensor:
+    """The columns ids [A] (int32, ascending, unique) of gemv(x, w), bit for bit, reading only those
+    rows of w (kd_gemv_gather): x [1, K] bf16, w [N, K] -> [1, A] bf16.  No epilogue, no fused norm.
+    Raises where gemv_gather_supported(N, K) is false."""
+    _require(x, torch.bfloat16, "gemv_gather.x")
+    _require(w, torch.bfloat16, "gemv_gather.w")
+    A = _gather_ids(ids, "gemv_gather")
+    if x.dim() != 2 or x.shape[0] != 1 or x.stride(1) != 1 or w.dim() != 2 or w.stride(1) != 1 or w.shape[1] != x.shape[1]:
+        raise RuntimeError("gemv_gather: x must be [1, K] and w [N, K], both with a contiguous last dim")
+    N, K = w.shape
+    y = torch.empty((1, A), dtype=torch.bfloat16, device=x.device)
+    NV.call("kd_gemv_gather", x.data_ptr(), w.data_ptr(), w.stride(0), ids.data_ptr(), A, y.data_ptr(), N, K, _stream())
+    return y
+
+
+def gemv_batch_gather(x: torch.Tensor, w: torch.Tensor, ids: torch.Tensor) -> torch.Tensor:
+    """The columns ids [A] (int32, ascending, unique) of gemv_batch(x, w), bit for bit, reading only
+    those rows of w (kd_gemv_batch_gather): x [nb, K] bf16, nb <= 16, w [N, K] -> [nb, A] bf16.  Row b
+    does not depend on nb or on the other rows.  Raises where gemv_gather_supported(N, K) is false."""
+    _require(x, torch.bfloat16, "gemv_batch_gather.x")
+    _require(w, torch.bfloat16, "gemv_batch_gather.w")
+    A = _gather_ids(ids, "gemv_batch_gather")
+    if x.dim() != 2 or x.stride(1) != 1 or w.dim() != 2 or w.stride(1) != 1 or w.shape[1] != x.shape[1]:
+        raise RuntimeError("gemv_batch_gather: x must be [nb, K] and w [N, K], both with a contiguous last dim")
+    nb, K = x.shape
+    N = w.shape[0]
+    y = torch.empty((nb, A), dtype=torch.bfloat16, device=x.device)
+    NV.call("kd_gemv_batch_gather", x.data_ptr(), max(x.stride(0), K), nb, w.data_ptr(), w.stride(0), ids.data_ptr(), A,
+            y.data_ptr(), N, K, _stream())
+    return y
+
+
+def gen_select_ids(scores: torch.Tensor, ids: torch.Tensor, seq: torch.Tensor, cur: torch.Tensor,
+                   repetition_penalty: float = 1.0, no_repeat_ngram_size: int = 0,
+                   out: torch.Tensor | None = None) -> None:
+    """gen_select_batch() among the allowed ids only (kd_gen_select_ids): scores [nb, A] bf16 (column j
+    the score of token ids[j]), ids [A] int32 ascending and unique, seq [nb, smax] int64, cur [nb]
+    int32; writes seq[b, cur[b]], out[b] and cur[b] += 1.  The lowest id wins a tie; token 0 if every
+    allowed id is banned."""
+    _require(scores, torch.bfloat16, "gen_select_ids.scores")
+    _require(seq, torch.int64, "gen_select_ids.seq")
+    _require(cur, torch.int32, "gen_select_ids.cur")
+    A = _gather_ids(ids, "gen_select_ids")
+    if scores.dim() != 2 or scores.shape[1] != A or scores.stride(1) != 1:
+        raise RuntimeError("gen_select_ids: scores must be [nb, A] with a contiguous last dim")
+    nb = scores.shape[0]
+    if seq.dim() != 2 or seq.shape[0] != nb or not seq.is_contiguous() or cur.numel() != nb or not cur.is_contiguous():
+        raise RuntimeError("gen_select_ids: seq contiguous [nb, smax], cur contiguous [nb]")
+    if out is not None:
+        _require(out, torch.int64, "gen_select_ids.out")
+        if out.numel() != nb or not out.is_contiguous():
+            raise RuntimeError("gen_select_ids: out must be a contiguous [nb] tensor")
+    NV.call("kd_gen_select_ids", scores.data_ptr(), max(scores.stride(0), A), ids.data_ptr(), A, seq.data_ptr(),
+            seq.shape[1], nb, cur.data_ptr(), float(repetition_penalty), int(no_repeat_ngram_size), _ptr(out), _stream())

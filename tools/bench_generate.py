@@ -17,7 +17,17 @@ prefill of one 336x336 prompt (L = 1536) + 32 greedy decode steps with the KV ca
     python tools/bench_generate.py --tree DIR    time the package of another checkout (the parent commit's, built) on
                                                  the same prompts: where it has no stop_check_every, the answer legs
                                                  time its plain calls with the same EOS ids (the baseline to
-                                                 interleave with)"""
+                                                 interleave with)
+    python tools/bench_generate.py --allowed 500,16384   constrained decoding: allowed_token_ids of A seeded ids against
+                                                 the unrestricted call, eos_token_id=() in both (the same number of
+                                                 steps), for generate() and, with --batch 16 / --grouped 6, for
+                                                 generate_batch() at --batch rows and generate_grouped(); each with the
+                                                 gathered head and with restrict_head=False (full head, then the
+                                                 allowed columns).  --allowed-only skips every other leg;
+                                                 --allowed-profile A runs one unrestricted and one restricted 32-token
+                                                 generate_batch() eagerly (graph=False) and nothing else: the run
+                                                 to put under a kernel trace (the two heads and selects have
+                                                 kernels of their own, every other kernel is the same in both)"""
 import argparse
 import inspect
 import sys
@@ -37,7 +47,14 @@ ap.add_argument("--rows-from-set", type=int, default=0, metavar="N",
                 help="answer legs also on the first N rows whose own K-th token is in the EOS set")
 ap.add_argument("--tree", default=None, metavar="DIR", help="import the package from this checkout instead")
 ap.add_argument("--answer-only", action="store_true", help="skip the other legs' 32 / 96-token sweeps")
+ap.add_argument("--allowed", default="", metavar="A[,A...]",
+                help="time allowed_token_ids sets of these sizes against the unrestricted calls")
+ap.add_argument("--allowed-only", action="store_true", help="only the --allowed legs (and the unrestricted calls in them)")
+ap.add_argument("--allowed-profile", type=int, default=0, metavar="A",
+                help="one eager unrestricted and one restricted generate_batch() of --batch rows, A allowed ids, nothing else")
 args = ap.parse_args()
+if args.allowed_only:
+    args.answer_only, args.answer_tokens = True, 0
 
 sys.path.insert(0, str(Path(args.tree).resolve() if args.tree else Path(__file__).resolve().parent.parent))
 from knowledge_distillation_for_sensory_substitution_in_multimodal_models_amd.data import synthetic_batch  # noqa
@@ -68,6 +85,23 @@ def timed(n_new):
     return best_of(lambda: generate(model, b["depth_input_ids"], b["depth_pixel_values"], b["image_sizes"],
                                     max_new_tokens=n_new, **kw))
 
+
+def allowed_set(A):
+    """A seeded ids of the vocabulary (the same set in every process)."""
+    g = torch.Generator().manual_seed(A)
+    return torch.randperm(STUDENT_05B.text.vocab, generator=g)[:A].tolist()
+
+
+if args.allowed_profile > 0:
+    rows = [synthetic_batch(1, dev, L=1536, seed=s) for s in range(max(1, min(args.batch, 16)))]
+    prompts = [(r["depth_input_ids"], r["depth_pixel_values"], r["image_sizes"]) for r in rows]
+    generate_batch(model, prompts, max_new_tokens=32, graph=False, **kw)
+    generate_batch(model, prompts, max_new_tokens=32, graph=False, allowed_token_ids=allowed_set(args.allowed_profile),
+                   **kw)
+    torch.cuda.synchronize()
+    print(f"eager generate_batch(), nb = {len(prompts)}, 32 new tokens: one unrestricted call, then one with "
+          f"{args.allowed_profile} allowed ids")
+    sys.exit(0)
 
 t32, t96 = timed(32), timed(96)
 t0 = time.perf_counter()
@@ -190,3 +224,35 @@ if args.answer_tokens > 0:
             return [o for g in outs for o in g]
         answer_leg(f"generate_grouped Q={args.grouped}", [(gi, q) for gi, g in enumerate(groups) for q in g[2]],
                    call_grouped)
+
+
+# ---------------------------------------------------------------- constrained decoding ----
+def allowed_leg(name, call):
+    """call(n_new, **kw) runs the entry point; eos_token_id=() everywhere, so every call runs n_new - 1 steps."""
+    def pair(**k):
+        t = [best_of(lambda: call(n, **k)) for n in (32, 96)]
+        return t[0] * 1e3, (t[1] - t[0]) / 64 * 1e3
+    free = [pair() for _ in range(3)]
+    f32, fstep = min(t for t, _ in free), min(s_ for _, s_ in free)
+    print(f"{name}, unrestricted, three times: " + "  ".join(f"{t:.2f} ms / step {s_:.3f} ms" for t, s_ in free) +
+          f"  (32 tokens per call / marginal step 32 -> 96; spread {(max(t for t, _ in free) / f32 - 1) * 100:.2f} %)")
+    if "allowed_token_ids" not in inspect.signature(generate).parameters:
+        print("  this tree has no allowed_token_ids: its unrestricted calls only (the baseline to interleave with)")
+        return
+    for A in [int(a) for a in args.allowed.split(",") if a]:
+        ids = allowed_set(A)
+        for tag, k in (("gathered head", {}), ("full head + columns (restrict_head=False)", dict(restrict_head=False))):
+            t, s_ = pair(allowed_token_ids=ids, **k)
+            print(f"  A = {A:5d}, {tag}: {t:.2f} ms per call ({(t / f32 - 1) * 100:+.2f} %), step {s_:.3f} ms "
+                  f"({(s_ - fstep) * 1e3:+.0f} us, {(s_ / fstep - 1) * 100:+.2f} %)")
+
+
+if args.allowed:
+    one = (b["depth_input_ids"], b["depth_pixel_values"], b["image_sizes"])
+    allowed_leg("generate", lambda n, **k: generate(model, *one, max_new_tokens=n, **kw, **k))
+    if args.batch > 0:
+        allowed_leg(f"generate_batch nb={len(prompts_b)}",
+                    lambda n, **k: generate_batch(model, prompts_b, max_new_tokens=n, **kw, **k))
+    if args.grouped > 0:
+        allowed_leg(f"generate_grouped Q={args.grouped} ({len(prompts)} prompts)",
+                    lambda n, **k: generate_grouped(model, groups, max_new_tokens=n, **kw, **k))
