@@ -284,6 +284,26 @@ size_t kd_gemm_workspace_size(const kd_gemm_desc* desc);
  * run unsplit before the split tail (0 = every tile split). */
 int kd_gemm_plan(const kd_gemm_desc* desc, int32_t* variant, int32_t* split_k, int32_t* dp_tiles);
 
+/* What a plan is chosen for.  KD_PLAN_LATENCY: the least modelled time of the call with the device to
+ * itself (waves of 256 workgroups; kd_gemm's and kd_gemm_plan's objective).  KD_PLAN_CU_TIME: the
+ * least modelled CU-time, tiles x splits x time per tile / 256 plus a split's partial planes and
+ * reduce launch -- what the call costs a step whose other streams fill the CUs it leaves free. */
+typedef enum { KD_PLAN_LATENCY = 0, KD_PLAN_CU_TIME = 1 } kd_plan_objective;
+
+/* The plan for `desc` under `objective`, with both modelled costs of that plan in microseconds
+ * (inspection only; no device work).  Objective 0 is kd_gemm_plan's answer.  Objective 1 chooses
+ * among the unsplit tile kernels (variant 2 / 3 / 4 / 16), keeps a forced desc->variant and a forced
+ * desc->split_k, and keeps objective 0's plan where the saving is under 5 % of its CU-time, where
+ * the descriptor does not run on the planned tiled kernels (fp8, row statistics, SwiGLU, pre-tiled
+ * B, v1, the variant codes other than 0 / 2 / 3 / 4 / 16) and where the unsplit launch cannot be
+ * forced (an output under 2^20 elements runs tiled only when split).  A returned plan that differs
+ * from objective 0's has dp_tiles = 0 and is launched as kd_gemm with desc->variant = *variant and
+ * desc->split_k = *split_k: kd_model_set_plan_objective does exactly that.  Costs are 0 for a plan
+ * the model has no constants for (v1, stream-K); on the v8-only routes they are the plain v8
+ * GEMM's of that shape. */
+int kd_gemm_plan_objective(const kd_gemm_desc* desc, int objective, int32_t* variant, int32_t* split_k,
+                           int32_t* dp_tiles, double* latency_us, double* cu_us);
+
 int kd_gemm(const kd_gemm_desc* desc, void* stream);
 
 /* ------------------------------------------------------------- attention ---- */
@@ -651,6 +671,16 @@ int kd_model_set_trainable(kd_model* m, int vision, int projector, int language)
  * forward / backward workspace sizes. */
 int kd_model_set_residual_f32(kd_model* m, int vision, int language);
 
+/* The objective (kd_plan_objective) the model's training GEMMs are planned for.  With
+ * KD_PLAN_CU_TIME every planned GEMM of a kd_model_forward that saves for a backward (save != 0)
+ * and of kd_model_backward -- the tower, projector and lm_head linears, the dgrads, the lane's
+ * ungrouped weight gradients -- runs kd_gemm_plan_objective's plan: for a training step that
+ * shares the device with other streams (a teacher forward, the weight-gradient lane).  A forward
+ * with save == 0 (a teacher, prefill, validation) always plans for latency, and the grouped weight
+ * gradients are one unsplit launch either way.  Changes which kernel runs and so the order of a
+ * GEMM's fp32 sums, nothing else.  Default KD_PLAN_LATENCY. */
+int kd_model_set_plan_objective(kd_model* m, int objective);
+
 /* fp8 teacher (BASELINE config c4): e4m3 copies of every linear weight the forward's GEMMs
  * read (all 2-D weights but the patch-embedding conv, the position embedding and
  * embed_tokens) in a uint8 buffer with the bf16 buffer's element offsets, plus one fp32
@@ -729,7 +759,8 @@ int kd_model_backward(kd_model* m, const void* fwd_workspace, const int64_t* ids
  * model runtime's) is bracketed by HIP events on its stream.  kd_timer_read synchronises
  * record i's end event and returns its key "<kind>:<M>x<N>x<K>:<f32|bf16>[:acc]", kind =
  * gemm_{k|n}{k|n} (A / B layout), gemm_kk_swiglu, gemm_f8 / gemm_f8_swiglu (fp8 path), its FLOPs
- * and milliseconds. */
+ * and milliseconds.  Inside a model call planned for CU-time (kd_model_set_plan_objective) a launch
+ * whose plan is still split-K carries ":s<splits>" at the end of its key. */
 void kd_timer_enable(int on);
 int kd_timer_count(void);
 int kd_timer_read(int i, char* key, int key_cap, double* flops, float* ms);

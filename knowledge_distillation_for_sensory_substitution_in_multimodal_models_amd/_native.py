@@ -149,6 +149,8 @@ SIGNATURES = {
     "kd_attn_bwd_workspace_size": (C.c_size_t, [C.POINTER(KdAttnBwdDesc)]),
     "kd_gemm_workspace_size": (C.c_size_t, [C.POINTER(KdGemmDesc)]),
     "kd_gemm_plan": (_i32, [C.POINTER(KdGemmDesc), C.POINTER(_i32), C.POINTER(_i32), C.POINTER(_i32)]),
+    "kd_gemm_plan_objective": (_i32, [C.POINTER(KdGemmDesc), _i32, C.POINTER(_i32), C.POINTER(_i32), C.POINTER(_i32),
+                                      C.POINTER(C.c_double), C.POINTER(C.c_double)]),
     "kd_norm_fwd": (_i32, [_i32, _vp, _i64, _vp, _vp, _vp, _i64, _vp, _vp, _i32, _i32, _f32, _i32, _vp]),
     "kd_norm_bwd_workspace_size": (_sz, [_i32, _i32]),
     "kd_norm_bwd": (_i32, [_i32, _vp, _i64, _vp, _vp, _i64, _vp, _vp, _vp, _i64, _i32, _vp, _vp, _i32, _vp, _sz,
@@ -211,6 +213,7 @@ SIGNATURES = {
     "kd_model_destroy": (None, [_vp]),
     "kd_model_set_trainable": (_i32, [_vp, _i32, _i32, _i32]),
     "kd_model_set_residual_f32": (_i32, [_vp, _i32, _i32]),
+    "kd_model_set_plan_objective": (_i32, [_vp, _i32]),
     "kd_model_fp8_scale_count": (_i64, [_vp]),
     "kd_model_quantize_fp8": (_i32, [_vp, _vp, _vp, _vp]),
     "kd_model_set_fp8": (_i32, [_vp, _vp, _vp]),

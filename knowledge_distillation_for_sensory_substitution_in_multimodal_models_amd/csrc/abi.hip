@@ -54,6 +54,16 @@ size_t kd_gemm_workspace_size(const kd_gemm_desc* desc) { return kd::gemm_worksp
 int kd_gemm_plan(const kd_gemm_desc* desc, int32_t* variant, int32_t* split_k, int32_t* dp_tiles) {
     return kd::gemm_plan_query(desc, variant, split_k, dp_tiles);
 }
+int kd_gemm_plan_objective(const kd_gemm_desc* desc, int objective, int32_t* variant, int32_t* split_k, int32_t* dp_tiles,
+                           double* latency_us, double* cu_us) {
+    KD_CHECK_ARG(variant && split_k && dp_tiles && latency_us && cu_us, "kd_gemm_plan_objective: null pointer");
+    kd::GemmObjectivePlan pl;
+    const int st = kd::gemm_plan_objective_query(desc, objective, &pl);
+    if (st != KD_OK) return st;
+    *variant = pl.variant; *split_k = pl.split_k; *dp_tiles = pl.dp_tiles;
+    *latency_us = pl.latency_us; *cu_us = pl.cu_us;
+    return KD_OK;
+}
 int kd_attn_fwd(const kd_attn_desc* d, void* s) { return kd::launch_attn_fwd(d, s); }
 int kd_attn_bwd(const kd_attn_bwd_desc* d, void* s) { return kd::launch_attn_bwd(d, s); }
 size_t kd_attn_bwd_workspace_size(const kd_attn_bwd_desc* d) { return kd::attn_bwd_workspace_size(d); }

@@ -20,6 +20,7 @@
 // [64 k][128 rows] read transposed by ds_read_b64_tr_b16.  Both conflict-free for the
 // 16x16x32 operand access pattern (derivation in DESIGN.md §GEMM).
 #include "common.h"
+#include "launchers.h"
 
 #include <cstring>
 #include <type_traits>
@@ -2099,11 +2100,16 @@ bool sk_fits(int64_t tiles, int64_t nk, const kd_gemm_desc* d) {
     return (tiles - dp) * nk >= 2 * SK_GRID && d->workspace && d->workspace_bytes >= sk_workspace_bytes(tiles - dp);
 }
 
-GemmPlan plan_gemm(const kd_gemm_desc* d, uint64_t ws_cap) {
-    const int64_t M = d->M, N = d->N;
-    const int64_t t256 = (int64_t)ceil_div(d->M, 256) * ceil_div(d->N, 256);
-    const int64_t tiles[5] = {t256, (int64_t)ceil_div(d->M, 256) * ceil_div(d->N, 128),
-                              (int64_t)ceil_div(d->M, 128) * ceil_div(d->N, 256), t256, t256};
+// The cost model's constants for one descriptor's operand layouts: plan_gemm (least isolated latency)
+// and plan_gemm_cu (least CU-time) price the same candidates with them.
+struct PlanModel {
+    const double* step;    // us per k-step of one tile, per candidate (v3 256x256, 256x128, 128x256; v8; v9)
+    const double* fixed;   // us per tile outside the k-loop, per candidate
+    double kBW, kSplitLaunch, split_pen;
+    int split_cap;
+    bool hybrid_on;
+};
+PlanModel plan_model(const kd_gemm_desc* d) {
     const bool kk = d->a_layout == KD_LAYOUT_K_MAJOR && d->b_layout == KD_LAYOUT_K_MAJOR;
     // per variant (v3 256x256, 256x128, 128x256; v8; v9): {K-major x K-major, MN-major operand}
     // refitted in round 4 to the step's CACHE STATE (profiles/r04/gemm_tune_cold.jsonl,
@@ -2128,9 +2134,20 @@ GemmPlan plan_gemm(const kd_gemm_desc* d, uint64_t ws_cap) {
     const double (&fixed_c)[2][5] = set3 ? fixed_c3 : fixed_c4;
     const double kBW = set3 ? 7.711e6 : 9.109e6;          // partial-plane bytes per microsecond
     const double kSplitLaunch = set3 ? 5.623 : 6.499;     // the reduce kernel (us); a hybrid plan launches two more kernels
+    return {step_c[kk ? 0 : 1], fixed_c[kk ? 0 : 1], kBW, kSplitLaunch, split_pen, split_cap, hybrid_on};
+}
+
+GemmPlan plan_gemm(const kd_gemm_desc* d, uint64_t ws_cap) {
+    const int64_t M = d->M, N = d->N;
+    const int64_t t256 = (int64_t)ceil_div(d->M, 256) * ceil_div(d->N, 256);
+    const int64_t tiles[5] = {t256, (int64_t)ceil_div(d->M, 256) * ceil_div(d->N, 128),
+                              (int64_t)ceil_div(d->M, 128) * ceil_div(d->N, 256), t256, t256};
+    const PlanModel pm = plan_model(d);
+    const double *step = pm.step, *fixed = pm.fixed;
+    const double kBW = pm.kBW, kSplitLaunch = pm.kSplitLaunch, split_pen = pm.split_pen;
+    const int split_cap = pm.split_cap;
+    const bool hybrid_on = pm.hybrid_on;
     constexpr bool kV9Auto = false;   // v9 enters the model's choice once its constants are fitted
-    const double* step = step_c[kk ? 0 : 1];
-    const double* fixed = fixed_c[kk ? 0 : 1];
     const int vcode[5] = {2, 3, 4, 16, 20};
     const int64_t nk = ceil_div(d->K, BK2);
     const VariantInfo* vi = variant_info(d->variant);
@@ -2220,6 +2237,79 @@ GemmRoute gemm_route(const kd_gemm_desc* d) {
     if (d->act == KD_ACT_DGELU_TANH || d->act == KD_ACT_DSWIGLU || d->qkv)
         d1.split_k = 1;   // the fused backward activation / q|k|v scatter are never split-K
     return {Route::TILED, plan_gemm(&d1, d->workspace ? d->workspace_bytes : 0)};
+}
+
+// ---- the second objective: least CU-time ----
+// plan_gemm prices a call that has the device to itself: waves of 256 workgroups, so a sub-wave output
+// is split over K to fill the CUs and a one-wave shape takes the tile that finishes soonest.  In the
+// training step two other streams fill whatever CUs a launch leaves free, and every tiled kernel holds
+// its CU alone (one workgroup per CU: launch bounds and 96-128 KB of LDS), so what a launch costs the
+// step is the CU-time it occupies: tiles x splits x (k-steps x step + fixed) / 256, plus a split's
+// partial planes and reduce launch -- no wave rounding.
+//
+// plan_cost prices one plan both ways with plan_model's constants; a plan the model has no constants
+// for (v1, stream-K, v8n) costs 0 / 0.
+struct PlanCost { double latency_us, cu_us; };
+PlanCost plan_cost(const kd_gemm_desc* d, const GemmPlan& pl) {
+    const int v = pl.var == 2 ? 0 : pl.var == 3 ? 1 : pl.var == 4 ? 2 : pl.var == 16 ? 3 : pl.var == 20 ? 4 : -1;
+    if (v < 0) return {0, 0};
+    const int tbm[5] = {256, 256, 128, 256, 256}, tbn[5] = {256, 128, 256, 256, 256};
+    const PlanModel pm = plan_model(d);
+    const int64_t tiles = (int64_t)ceil_div(d->M, tbm[v]) * ceil_div(d->N, tbn[v]);
+    const int64_t nk = ceil_div(d->K, BK2), S = pl.split, kcs = S > 1 ? ceil_div(pl.kchunk, BK2) : nk;
+    const double whole = (double)nk * pm.step[v] + pm.fixed[v], part = (double)kcs * pm.step[v] + pm.fixed[v];
+    const double out_e = (double)((d->c_dtype == KD_DTYPE_F32 ? 4 : 2) * (d->accumulate ? 2 : 1) +
+                                  (d->residual ? (d->residual_dtype == KD_DTYPE_F32 ? 4 : 2) : 0) + (d->aux ? 2 : 0));
+    const int64_t dp = S > 1 ? pl.dp_tiles : 0, tail = tiles - dp;
+    const double elems = dp ? (double)tail * tbm[v] * tbn[v] : (double)d->M * d->N;   // the split part of C
+    const double fold = S > 1 ? ((double)S * elems * 8 * pm.split_pen + elems * out_e) / pm.kBW + (dp ? 2 : 1) * pm.kSplitLaunch : 0;
+    const double lat = (double)(dp / 256) * whole + (double)((tail * S + 255) / 256) * part + fold;
+    const double cu = ((double)dp * whole + (double)tail * S * part) / 256 + fold;
+    return {lat, cu};
+}
+
+// A CU-time plan replaces the latency plan only where it saves at least this fraction of the latency
+// plan's CU-time: below it the two are within the fit's error (tools/fit_plan.py: picks within 0.4 % of
+// the measured best per step, single shapes off by a few percent), and the latency plan is the one
+// measured in the step.  Every changed pick of the c1 step saves 15 % or more; any margin from 3 % to
+// 10 % gives the same picks there.
+constexpr double kCuMargin = 0.05;
+
+// The plan of a descriptor under an objective (0: plan_gemm's, least isolated latency; 1: least
+// CU-time) with both modelled costs.  Objective 1 chooses among the unsplit tile kernels (v3 256x256 /
+// 256x128 / 128x256, v8) -- a split never has less CU-time than the same tile unsplit -- and keeps
+// a forced variant / split_k.  The choice is handed on as an ordinary forced descriptor (`forced`:
+// launch with variant = plan.var, split_k = plan.split), so its bits are that forced launch's; a
+// choice the descriptor cannot force (an output under 2^20 elements is tiled only when split, see
+// tiled_ok) keeps the latency plan, as does every route but TILED and every variant code outside
+// 0 / 2 / 3 / 4 / 16.
+GemmObjectivePlan plan_gemm_objective(const kd_gemm_desc* d, int objective) {
+    const GemmRoute r0 = gemm_route(d);
+    const PlanCost c0 = plan_cost(d, r0.plan);
+    const GemmObjectivePlan keep{r0.plan.var, r0.plan.split, r0.plan.dp_tiles, c0.latency_us, c0.cu_us, false};
+    const int fv = d->variant;
+    if (objective == 0 || r0.route != Route::TILED || !(fv == 0 || fv == 2 || fv == 3 || fv == 4 || fv == 16)) return keep;
+    GemmObjectivePlan best = keep;
+    bool found = false;
+    for (int code : {2, 3, 4, 16}) {
+        if (fv != 0 && code != fv) continue;
+        kd_gemm_desc df = *d;
+        df.variant = code;
+        df.split_k = d->split_k > 1 ? d->split_k : 1;
+        const GemmRoute r = gemm_route(&df);
+        if (r.route != Route::TILED || r.plan.var != code) continue;
+        const PlanCost c = plan_cost(&df, r.plan);
+        if (!found || c.cu_us < best.cu_us) {
+            best = GemmObjectivePlan{r.plan.var, r.plan.split, r.plan.dp_tiles, c.latency_us, c.cu_us, true};
+            found = true;
+        }
+    }
+    if (!found || best.cu_us > c0.cu_us) return keep;
+    if (best.variant == keep.variant && best.split_k == keep.split_k && best.dp_tiles == keep.dp_tiles) return keep;
+    // the margin holds for a latency plan that is itself a candidate (unsplit, or split because forced)
+    const bool lat_is_candidate = r0.plan.dp_tiles == 0 && (r0.plan.split == 1 || d->split_k > 1);
+    if (lat_is_candidate && best.cu_us > c0.cu_us * (1.0 - kCuMargin)) return keep;
+    return best;
 }
 
 // The kernel parameters every launch path shares; a path then sets only what is its own.  Value-
@@ -2709,6 +2799,14 @@ int gemm_plan_query(const kd_gemm_desc* d, int32_t* var, int32_t* split, int32_t
     KD_CHECK_SHAPE(d->M > 0 && d->N > 0 && d->K > 0, "gemm_plan: empty shape");
     const GemmPlan pl = gemm_route(d).plan;
     *var = pl.var; *split = pl.split; *dp = pl.dp_tiles;
+    return KD_OK;
+}
+
+int gemm_plan_objective_query(const kd_gemm_desc* d, int objective, GemmObjectivePlan* out) {
+    KD_CHECK_ARG(d && out, "gemm_plan_objective: null pointer");
+    KD_CHECK_ARG(objective == KD_PLAN_LATENCY || objective == KD_PLAN_CU_TIME, "gemm_plan_objective: objective must be 0 or 1");
+    KD_CHECK_SHAPE(d->M > 0 && d->N > 0 && d->K > 0, "gemm_plan_objective: empty shape");
+    *out = plan_gemm_objective(d, objective);
     return KD_OK;
 }
 

@@ -24,6 +24,10 @@ size_t gemm_workspace_size(const kd_gemm_desc* d);
 size_t gemm_pretile_size(int N, int K, int glu);
 int launch_gemm_pretile(const void* W, int64_t ldw, int N, int K, int glu, void* out, void* stream);
 int gemm_plan_query(const kd_gemm_desc* d, int32_t* var, int32_t* split, int32_t* dp);
+// The plan under an objective (KD_PLAN_LATENCY / KD_PLAN_CU_TIME) and its two modelled costs.  forced:
+// the plan differs from the descriptor's own and is launched by setting variant / split_k to it.
+struct GemmObjectivePlan { int variant, split_k, dp_tiles; double latency_us, cu_us; bool forced; };
+int gemm_plan_objective_query(const kd_gemm_desc* d, int objective, GemmObjectivePlan* out);
 int launch_attn_fwd(const kd_attn_desc* d, void* stream);
 int launch_attn_bwd(const kd_attn_bwd_desc* d, void* stream);
 size_t attn_bwd_workspace_size(const kd_attn_bwd_desc* d);

@@ -43,6 +43,18 @@ struct TimerRec {
 std::mutex g_timer_mu;
 std::vector<TimerRec> g_timer;
 bool g_timer_on = false;
+
+// The objective the runtime's GEMMs are planned for while a kd_model_forward (save != 0) /
+// kd_model_backward of a model with kd_model_set_plan_objective(KD_PLAN_CU_TIME) is issuing them on
+// this thread; KD_PLAN_LATENCY everywhere else (PlanScope sets it for the length of such a call).
+thread_local int t_plan_objective = KD_PLAN_LATENCY;
+struct PlanScope {
+    const int prev = t_plan_objective;
+    explicit PlanScope(int objective) { t_plan_objective = objective; }
+    ~PlanScope() { t_plan_objective = prev; }
+    PlanScope(const PlanScope&) = delete;
+    PlanScope& operator=(const PlanScope&) = delete;
+};
 }  // namespace
 
 int gemm_timed(const kd_gemm_desc* d, void* stream) {
@@ -58,6 +70,10 @@ int gemm_timed(const kd_gemm_desc* d, void* stream) {
                                                         (dact ? "_dact" : ""));
     r.key += ":" + std::to_string(d->M) + "x" + std::to_string(d->N) + "x" + std::to_string(d->K) + ":" +
              (d->c_dtype == KD_DTYPE_F32 ? "f32" : "bf16") + (d->accumulate ? ":acc" : "");
+    if (t_plan_objective == KD_PLAN_CU_TIME) {   // a split-K launch that is left under the CU-time objective: ":s<splits>"
+        int32_t var = 0, split = 1, dp = 0;
+        if (gemm_plan_query(d, &var, &split, &dp) == KD_OK && split > 1) r.key += ":s" + std::to_string(split);
+    }
     r.flops = 2.0 * d->M * d->N * d->K;
     (void)hipEventCreate(&r.e0);
     (void)hipEventCreate(&r.e1);
@@ -225,6 +241,7 @@ struct kd_model {
     // one planned kd_gemm each), and (A/B, with grouping off) KD_WGRAD_V8_UNSPLIT=1: each of them
     // alone on the group's kernel -- v8 tiles, unsplit, one launch per GEMM, the group's bits
     int lane_group = 1, lane_v8_unsplit = 0;
+    int plan_objective = KD_PLAN_LATENCY;   // kd_model_set_plan_objective: what the training GEMMs are planned for
     // fp32 residual streams (kd_model_set_residual_f32): the SigLIP / Qwen2 hidden state x that
     // every layer adds into is kept in fp32 (GEMM epilogues add the residual in fp32 and write
     // fp32; the norms read fp32) instead of being rounded to bf16 after every add
@@ -308,6 +325,12 @@ struct GemmArgs {
     float rs_inv_t = 1.f;
 };
 
+#define KD_TRY(x)                    \
+    do {                             \
+        const int st__ = (x);        \
+        if (st__ != KD_OK) return st__; \
+    } while (0)
+
 // split-K default of the runtime's GEMMs (KD_GEMM_SPLIT_K: 0 = the cost model, 1 = never split)
 static const int g_split_default = ab_knob("KD_GEMM_SPLIT_K", 0);
 
@@ -331,6 +354,11 @@ int gemm(hipStream_t s, void* ws, int M, int N, int K, Op a, Op b, void* C, int6
     d.split_k = g.split_k ? g.split_k : g_split_default;
     if (d.split_k != 1 && ws) { d.workspace = ws; d.workspace_bytes = SPLITK_WS; }
     d.row_stats = g.row_stats; d.row_stats_vs = g.rs_vs; d.row_stats_inv_t = g.rs_inv_t; d.row_stats_top2 = g.rs_top2;
+    if (t_plan_objective == KD_PLAN_CU_TIME) {   // the CU-time plan, handed on as a forced descriptor
+        GemmObjectivePlan pl;
+        KD_TRY(gemm_plan_objective_query(&d, KD_PLAN_CU_TIME, &pl));
+        if (pl.forced) { d.variant = pl.variant; d.split_k = pl.split_k; }
+    }
     return gemm_timed(&d, s);
 }
 
@@ -340,12 +368,6 @@ static const bool g_fuse_dact = ab_knob("KD_FUSE_DACT", 1) != 0;
 static bool fused_dact_ok(int64_t M, int64_t N) {
     return g_fuse_dact && M >= 128 && N >= 128 && N % 8 == 0 && M * N >= (int64_t)1 << 20;
 }
-
-#define KD_TRY(x)                    \
-    do {                             \
-        const int st__ = (x);        \
-        if (st__ != KD_OK) return st__; \
-    } while (0)
 
 // the weight-gradient lane: a second stream ordered after the dgrad chain at each hand-off
 struct Lane {
@@ -1209,6 +1231,14 @@ static bool fp8_stream_ok(bool f8, int fam, int rf32_v, int rf32_t) {
     return !f8 || ((!rf32_v || !(fam & KD_FP8_VISION)) && (!rf32_t || !(fam & (KD_FP8_LM_ATTN | KD_FP8_LM_MLP))));
 }
 
+int kd_model_set_plan_objective(kd_model* m, int objective) {
+    KD_CHECK_ARG(m, "kd_model_set_plan_objective: null model");
+    KD_CHECK_ARG(objective == KD_PLAN_LATENCY || objective == KD_PLAN_CU_TIME,
+                 "kd_model_set_plan_objective: objective must be KD_PLAN_LATENCY or KD_PLAN_CU_TIME");
+    m->plan_objective = objective;
+    return KD_OK;
+}
+
 int kd_model_set_residual_f32(kd_model* m, int vision, int language) {
     KD_CHECK_ARG(m, "kd_model_set_residual_f32: null model");
     KD_CHECK_ARG(fp8_stream_ok(m->f8q, m->f8_families, vision, language),
@@ -1284,6 +1314,9 @@ int kd_model_forward(kd_model* m, const int64_t* ids, const void* pixels, int pi
     KD_CHECK_ARG(pixel_dtype == KD_DTYPE_BF16 || pixel_dtype == KD_DTYPE_F32, "kd_model_forward: pixel dtype");
     const FwdPlan P = plan_forward(m, B, L, n_tiles, save, workspace);
     KD_CHECK_ARG(workspace_bytes >= P.bytes, "kd_model_forward: workspace too small");
+    // only a forward that saves for a backward is part of a training step; a teacher, prefill and
+    // validation (save == 0) plan for latency whatever the switch says
+    const PlanScope plan_scope(save ? m->plan_objective : KD_PLAN_LATENCY);
     const kd_model_config& c = m->C.c;
     hipStream_t s = as_stream(stream);
     const int NI = n_tiles, M = B * L, H = c.t_hidden;
@@ -1325,6 +1358,7 @@ int kd_model_backward(kd_model* m, const void* fwd_workspace, const int64_t* ids
     const FwdPlan F = plan_forward(m, B, L, n_tiles, 1, const_cast<void*>(fwd_workspace));
     const BwdPlan P = plan_backward(m, B, L, n_tiles, workspace);
     KD_CHECK_ARG(workspace_bytes >= P.bytes, "kd_model_backward: workspace too small");
+    const PlanScope plan_scope(m->plan_objective);
     const kd_model_config& c = m->C.c;
     hipStream_t s = as_stream(stream);
     Lane lane{m, s, as_stream(wgrad_stream), P.splitk_lane};

@@ -272,6 +272,11 @@ class _KDBase(_Base):
         if state_dict is not None:
             self.load_kd_state_dict(state_dict)
         self.config = self.student_model.cfg
+        # the student's training GEMMs are planned for CU-time, not for the latency of each call alone:
+        # the step runs them beside the teacher forward and the weight-gradient lane, which fill the
+        # CUs a launch leaves free.  cu_time_plans = False plans them for latency
+        # again: for A/B runs, and for training on one stream with nothing beside it
+        self.cu_time_plans = True
         self._anchor = nn.Parameter(torch.zeros((), device=dev))
         # one stream for all student work (forward, backward dgrad chain, AdamW, zero_grad):
         # they are a dependency chain anyway, and HIP multiplexes more streams than hardware
@@ -622,6 +627,16 @@ class _KDBase(_Base):
             self.teacher_model.P.load_state_dict(sd, prefix="teacher_model.")
             if getattr(self.teacher_model, "fp8", False):
                 self.teacher_model.enable_fp8(self.teacher_model.fp8_families)   # re-quantise the new weights
+
+    @property
+    def cu_time_plans(self) -> bool:
+        """Whether the student's saved forward and backward plan their GEMMs for CU-time
+        (LlavaOnevisionModel.set_plan_objective); the teacher and every unsaved forward never do."""
+        return self.student_model.plan_objective == 1
+
+    @cu_time_plans.setter
+    def cu_time_plans(self, on: bool):
+        self.student_model.set_plan_objective(1 if on else 0)
 
     def load_hf_weights(self, student: dict | None = None, teacher: dict | None = None, strict: bool = True):
         """The weights `from_pretrained(model_name_*)` would load (DT:33-48), given as

@@ -444,6 +444,7 @@ class LlavaOnevisionModel:
         self.residual_f32 = (False, False)
         self.fp8_families = 0
         self.lm_stream_f32 = False
+        self.plan_objective = 0
         self.set_residual_f32(*self._default_streams())
 
     def set_residual_f32(self, vision: bool, language: bool):
@@ -451,6 +452,13 @@ class LlavaOnevisionModel:
         NV.call("kd_model_set_residual_f32", self._h, int(vision), int(language))
         self.residual_f32 = (bool(vision), bool(language))
         self._ws = {}   # the workspaces' stream buffers change size
+
+    def set_plan_objective(self, objective: int):
+        """What the GEMMs of a saved forward and of the backward are planned for: 0 the least latency
+        of each call alone, 1 the least CU-time (kd_model_set_plan_objective) -- for a training step
+        that shares the device with other streams.  A forward that does not save always plans for latency."""
+        NV.call("kd_model_set_plan_objective", self._h, int(objective))
+        self.plan_objective = int(objective)
 
     def __del__(self):
         h = getattr(self, "_h", None)

@@ -33,7 +33,9 @@ class KernelTimer:
         NV.lib().kd_timer_reset()
 
     def records(self):
-        """[(key, flops, ms)], key = "<kind>:<M>x<N>x<K>:<out dtype>[:acc]" (synchronises)."""
+        """[(key, flops, ms)], key = "<kind>:<M>x<N>x<K>:<out dtype>[:acc]" (synchronises); a grouped
+        weight-gradient launch ends in ":g<members>", and a launch whose plan is still split-K inside a model
+        call planned for CU-time (kd_model_set_plan_objective) in ":s<splits>"."""
         lib = NV.lib()
         key = C.create_string_buffer(128)
         fl, ms = C.c_double(), C.c_float()
@@ -305,6 +307,19 @@ def gemm_plan(a: torch.Tensor, b: torch.Tensor, out: torch.Tensor | None = None,
     v, s_, dp = C.c_int32(), C.c_int32(), C.c_int32()
     NV.call("kd_gemm_plan", C.byref(d), C.byref(v), C.byref(s_), C.byref(dp))
     return v.value, s_.value, dp.value
+
+
+def gemm_plan_objective(objective: int, a: torch.Tensor, b: torch.Tensor, out: torch.Tensor | None = None, **kw):
+    """gemm_plan() under an objective (0 least latency = gemm_plan, 1 least CU-time): (kernel variant,
+    K splits, unsplit leading tiles, modelled latency us, modelled CU-time us) -- kd_gemm_plan_objective."""
+    kw = {"bias": None, "act": None, "residual": None, "aux": None, "alpha": 1.0, "alpha_dev": None, "accumulate": False,
+          "out_dtype": torch.bfloat16, "residual_row_mod": 0, "variant": 0, "split_k": 0, **kw}
+    d = _gemm_desc(a, b, out, kw["bias"], kw["act"], kw["residual"], kw["aux"], kw["alpha"], kw["alpha_dev"],
+                   kw["accumulate"], kw["out_dtype"], kw["residual_row_mod"], kw["variant"], kw["split_k"])[0]
+    v, s_, dp, lat, cu = C.c_int32(), C.c_int32(), C.c_int32(), C.c_double(), C.c_double()
+    NV.call("kd_gemm_plan_objective", C.byref(d), int(objective), C.byref(v), C.byref(s_), C.byref(dp), C.byref(lat),
+            C.byref(cu))
+    return v.value, s_.value, dp.value, lat.value, cu.value
 
 
 _SPLIT_DEFAULT = [0]
