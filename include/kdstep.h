@@ -611,6 +611,46 @@ int kd_gen_select_ids(const void* scores, int64_t ld_scores, const int32_t* ids,
                       int nb, int32_t* cur_dev, float repetition_penalty, int no_repeat_ngram, int64_t* out,
                       void* stream);
 
+/* Sampling (do_sample=True of generate() / generate_batch() / generate_grouped()): the token is
+ * drawn, not the argmax: transformers' _sample (TemperatureLogitsWarper, TopKLogitsWarper,
+ * TopPLogitsWarper behind the processors above, then torch.multinomial), made reproducible.
+ * Stream-ordered, no host sync, fixed arguments across steps (one captured graph replays the
+ * step), bit-deterministic and batch invariant in the sense above: one workgroup owns a row, the
+ * grid is the batch, and every sum is an integer sum (no floating-point atomics).
+ * kd_gen_sample: scores [nb, N] bf16 (rows ld_scores >= N apart), 1 <= nb <= 16.  ids == NULL:
+ *   column j is token j (1 <= N <= 262144) and the processors follow kd_gen_select_batch; with ids
+ *   (device int32 [N], ascending and unique, 1 <= N <= KD_GEN_ALLOWED_MAX) column j is token
+ *   ids[j] and they follow kd_gen_select_ids.  Per row, in this order:
+ *   1. processed scores s_j in fp32: repetition penalty (s < 0 ? s * p : s / p, correctly
+ *      rounded) and the no-repeat-n-gram ban (-inf), exactly as the select kernels build them;
+ *   2. t_j = s_j / temperature (fp32, correctly rounded; temperature finite and > 0); NaN counts
+ *      as -inf;
+ *   3. top_k >= 1: keep every j with t_j >= the top_k-th largest t (ties at that value are all
+ *      kept); top_k >= N keeps everything, 0 is off;
+ *   4. top_p < 1: with p = softmax(t) over what 3 kept, keep j iff the entries with a strictly
+ *      larger score have mass < top_p.  Equal scores are kept or dropped together; the largest
+ *      entry is always kept;
+ *   5. w_j = exp(t_j - max t) for kept j (0 otherwise), Z = sum w_j, C_j the inclusive cumulative
+ *      weight in ascending id order: the token is the smallest id j with C_j > u * Z.  An entry of
+ *      weight 0 is never chosen; no score above -inf: token 0.  The kernel holds each w_j as
+ *      floor(w_j * 2^40) in 64 bits, so Z, the masses of 4 and C_j are exact integer sums;
+ *   6. u = (x >> 8) * 2^-24, x = word 0 of Philox4x32-10 with key (seed & 0xffffffff, seed >> 32)
+ *      and counter (pos, stream & 0xffffffff, stream >> 32, 0); pos = cur_dev[b] before the
+ *      increment (the index the token is written to), stream = streams[b] (device int64 [nb]).
+ *   Writes as kd_gen_select_batch: seq[b][cur_dev[b]], out[b], cur_dev[b] += 1; a full row
+ *   (cur_dev[b] == smax) gets out[b] and cur_dev[b] = smax + 1 but no element of seq; u_out[b]
+ *   (optional, device fp32 [nb]) receives the row's u.  workspace (16-byte aligned) >=
+ *   kd_gen_sample_workspace_size(nb, N) bytes (0 for an nb or N out of range): per row the fp32
+ *   row t, the fixed-point weights and their 256-id tile sums stay there between the passes.
+ *   Null pointers (ids and u_out excepted), penalty <= 0, ngram < 0, temperature not finite or
+ *   <= 0, top_k < 0, top_p outside (0, 1] -> KD_ERR_ARG; nb, N, smax, ld_scores or the workspace
+ *   size out of range -> KD_ERR_SHAPE; both before any device work. */
+size_t kd_gen_sample_workspace_size(int nb, int N);
+int kd_gen_sample(const void* scores, int64_t ld_scores, int N, const int32_t* ids, int64_t* seq, int smax, int nb,
+                  int32_t* cur_dev, float repetition_penalty, int no_repeat_ngram, float temperature, int top_k,
+                  float top_p, uint64_t seed, const int64_t* streams, void* workspace, size_t workspace_bytes,
+                  int64_t* out, float* u_out, void* stream);
+
 /* --------------------------------------------------------- model runtime ---- */
 /* One LLaVA-OneVision instance (SigLIP -> projector -> anyres pack -> Qwen2 -> lm_head)
  * whose forward and backward layer loops run in the library (SURVEY §8b "teacher forward"

@@ -125,7 +125,7 @@ class KdError(RuntimeError):
         self.code = code
 
 
-_vp, _i32, _i64, _sz, _f32 = C.c_void_p, C.c_int, C.c_int64, C.c_size_t, C.c_float
+_vp, _i32, _i64, _sz, _f32, _u64 = C.c_void_p, C.c_int, C.c_int64, C.c_size_t, C.c_float, C.c_uint64
 
 # name -> (restype, argtypes).  Kept in the same order as include/kdstep.h.
 KD_GEMV_ROWS_MAX = 1024   # include/kdstep.h: rows per kd_gemv_rows / kd_attn_extend call
@@ -202,6 +202,9 @@ SIGNATURES = {
     "kd_gemv_gather": (_i32, [_vp, _vp, _i64, _vp, _i32, _vp, _i32, _i32, _vp]),
     "kd_gemv_batch_gather": (_i32, [_vp, _i64, _i32, _vp, _i64, _vp, _i32, _vp, _i32, _i32, _vp]),
     "kd_gen_select_ids": (_i32, [_vp, _i64, _vp, _i32, _vp, _i32, _i32, _vp, _f32, _i32, _vp, _vp]),
+    "kd_gen_sample_workspace_size": (_sz, [_i32, _i32]),
+    "kd_gen_sample": (_i32, [_vp, _i64, _i32, _vp, _vp, _i32, _i32, _vp, _f32, _i32, _f32, _i32, _f32, _u64, _vp, _vp,
+                             _sz, _vp, _vp, _vp]),
     "kd_image_resize_u8": (_i32, [_vp, _i32, _i32, _vp, _i32, _i32, _vp, _sz, _vp]),
     "kd_anyres_tiles": (_i32, [_vp, _vp, _i32, _i32, _i32, _i32, _i32, _i32, _vp, _vp, _i32, _vp]),
     "kd_anyres_batch_map": (_i32, [_vp, _i32, _i32, _vp, _i32, _vp]),

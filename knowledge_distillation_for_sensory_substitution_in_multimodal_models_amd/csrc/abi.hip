@@ -217,6 +217,13 @@ int kd_gen_select_ids(const void* scores, int64_t lds, const int32_t* ids, int A
                       int32_t* cur, float penalty, int ngram, int64_t* out, void* s) {
     return kd::launch_gen_select_ids(scores, lds, ids, A, seq, smax, nb, cur, penalty, ngram, out, s);
 }
+size_t kd_gen_sample_workspace_size(int nb, int N) { return kd::gen_sample_ws(nb, N); }
+int kd_gen_sample(const void* scores, int64_t lds, int N, const int32_t* ids, int64_t* seq, int smax, int nb, int32_t* cur,
+                  float penalty, int ngram, float temperature, int top_k, float top_p, uint64_t seed,
+                  const int64_t* streams, void* ws, size_t wsb, int64_t* out, float* u_out, void* s) {
+    return kd::launch_gen_sample(scores, lds, N, ids, seq, smax, nb, cur, penalty, ngram, temperature, top_k, top_p, seed,
+                                 streams, ws, wsb, out, u_out, s);
+}
 size_t kd_image_resize_workspace_size(int H, int W, int oh, int ow) { return kd::image_resize_ws(H, W, oh, ow); }
 int kd_image_resize_u8(const uint8_t* in, int H, int W, uint8_t* out, int oh, int ow, void* ws, size_t ws_bytes,
                        void* s) {

@@ -19,12 +19,17 @@
 // row the same bits) and k_attn_extend_part (ragged suffix queries against prefix + own suffix);
 // and for an allowed set of token ids (the evaluation's RestrictedLogitsProcessor,
 // evaluate_onevision.py:141-158) k_gemv_gather / k_gemv_batch_gather (the lm_head over the allowed
-// rows only, with the full head's bits) and k_gen_select_ids (the choice among the allowed ids).
+// rows only, with the full head's bits) and k_gen_select_ids (the choice among the allowed ids);
+// and for do_sample=True k_gen_sample (temperature, top-k, top-p and a Philox draw in place of the
+// argmax, over a full row or the compact allowed row).
 //
 // Each algorithm has one body.  The single-row and the batched form of a kernel differ in where a
 // row's pointers and length come from, not in what is computed, so they share a __forceinline__
 // device function and keep only their own setup and stores:
 //   gen_select_row   flags, processors, argmax: k_gen_select, k_gen_select_batch
+//   gen_flags_row, gen_flags_ids, gen_processed
+//                    the processors' flag passes and the processed score of an entry: the selects
+//                    and k_gen_sample
 //   gb_row_rstd, gb_stage_slab, gb_wave_order_sum, gb_store
 //                    the 16-row slab of k_gemv_batch and k_gemv_slabs, which is why a row of
 //                    kd_gemv_rows has kd_gemv_batch's bits; k_gemv_batch_reduce serves both
@@ -37,6 +42,7 @@
 
 #include <algorithm>
 #include <climits>
+#include <cmath>
 #include <string>
 #include <type_traits>
 
@@ -261,10 +267,9 @@ __global__ void __launch_bounds__(NT) k_gemv_wide(const bf16* __restrict__ x, co
 // bit 1 = banned) from the len ids of seq, then the processed-score argmax, which thread 0 returns
 // (the other threads' value is not the row's).  The vector paths need 16-byte aligned logits and
 // flags (the single-row workspace always is; row b of a batch may not be) and fall back to bytes.
-__device__ __forceinline__ int gen_select_row(const bf16* __restrict__ logits, int V, const int64_t* __restrict__ seq,
-                                              int len, float penalty, int ngram, uint8_t* __restrict__ flags) {
-    __shared__ float sv[16];
-    __shared__ int si[16];
+// The flag pass of gen_select_row, shared with the sampling kernel (k_gen_sample): ends on a barrier.
+__device__ __forceinline__ void gen_flags_row(int V, const int64_t* __restrict__ seq, int len, float penalty, int ngram,
+                                              uint8_t* __restrict__ flags) {
     {   // clear the flags, 16 B per store
         const int v16 = ((uintptr_t)flags & 15) == 0 ? V >> 4 : 0;
         for (int i = threadIdx.x; i < v16; i += blockDim.x) ((u32x4*)flags)[i] = u32x4{0u, 0u, 0u, 0u};
@@ -290,11 +295,25 @@ __device__ __forceinline__ int gen_select_row(const bf16* __restrict__ logits, i
             }
         }
     __syncthreads();
+}
+
+// The processed fp32 score of one entry from its flags (bit 0 = seen: the repetition penalty,
+// correctly rounded; bit 1 = banned): every token choice, greedy or sampled, goes through this.
+__device__ __forceinline__ float gen_processed(float s, uint32_t f, float penalty) {
+    if (f & 1) s = s < 0.f ? __fmul_rn(s, penalty) : __fdiv_rn(s, penalty);
+    if (f & 2) s = -INFINITY;
+    return s;
+}
+
+__device__ __forceinline__ int gen_select_row(const bf16* __restrict__ logits, int V, const int64_t* __restrict__ seq,
+                                              int len, float penalty, int ngram, uint8_t* __restrict__ flags) {
+    __shared__ float sv[16];
+    __shared__ int si[16];
+    gen_flags_row(V, seq, len, penalty, ngram, flags);
     float best = -INFINITY;
     int bi = 0x7fffffff;
     auto consider = [&](int i, float s, uint32_t f) {
-        if (f & 1) s = s < 0.f ? __fmul_rn(s, penalty) : __fdiv_rn(s, penalty);
-        if (f & 2) s = -INFINITY;
+        s = gen_processed(s, f, penalty);
         if (s > best || (s == best && i < bi)) { best = s; bi = i; }   // NaN never wins
     };
     // 8 logits (16 B) + 8 flags per step
@@ -1037,23 +1056,10 @@ __device__ __forceinline__ int ids_find(const int* __restrict__ ids, int A, int6
     return lo < A && (int64_t)ids[lo] == t ? lo : -1;
 }
 
-// k_gen_select_batch over compact scores [nb, A] (column j: token ids[j]): row b = blockIdx.x.  The
-// flags (bit 0 = seen, bit 1 = banned) are kept per allowed entry in LDS, and every id of the
-// sequence is looked up in ids by binary search (a miss touches nothing), so the cost follows A
-// and the row's length, never V.  Ascending ids: the lowest entry on a tie is the lowest id.  No
-// finite allowed score: token 0, as the argmax of an all -inf row of V logits.
-__global__ void __launch_bounds__(1024) k_gen_select_ids(const bf16* __restrict__ scores_all, int64_t lds,
-                                                         const int* __restrict__ ids, int A,
-                                                         int64_t* __restrict__ seq_all, int smax,
-                                                         int* __restrict__ cur_dev, float penalty, int ngram,
-                                                         int64_t* __restrict__ out) {
-    __shared__ uint8_t flags[KD_GEN_ALLOWED_MAX];
-    __shared__ float sv[16];
-    __shared__ int si[16];
-    const int b = blockIdx.x;
-    int64_t* seq = seq_all + (size_t)b * smax;
-    const bf16* scores = scores_all + (size_t)b * lds;
-    const int len = max(0, min(cur_dev[b], smax));   // the ids read never leave the row
+// The flag pass of k_gen_select_ids over the A allowed entries (flags in LDS), shared with the
+// sampling kernel (k_gen_sample): ends on a barrier.
+__device__ __forceinline__ void gen_flags_ids(const int* __restrict__ ids, int A, const int64_t* __restrict__ seq,
+                                              int len, float penalty, int ngram, uint8_t* flags) {
     for (int i = threadIdx.x; i < A; i += blockDim.x) flags[i] = 0;
     __syncthreads();
     if (penalty != 1.0f)
@@ -1072,13 +1078,30 @@ __global__ void __launch_bounds__(1024) k_gen_select_ids(const bf16* __restrict_
             }
         }
     __syncthreads();
+}
+
+// k_gen_select_batch over compact scores [nb, A] (column j: token ids[j]): row b = blockIdx.x.  The
+// flags (bit 0 = seen, bit 1 = banned) are kept per allowed entry in LDS, and every id of the
+// sequence is looked up in ids by binary search (a miss touches nothing), so the cost follows A
+// and the row's length, never V.  Ascending ids: the lowest entry on a tie is the lowest id.  No
+// finite allowed score: token 0, as the argmax of an all -inf row of V logits.
+__global__ void __launch_bounds__(1024) k_gen_select_ids(const bf16* __restrict__ scores_all, int64_t lds,
+                                                         const int* __restrict__ ids, int A,
+                                                         int64_t* __restrict__ seq_all, int smax,
+                                                         int* __restrict__ cur_dev, float penalty, int ngram,
+                                                         int64_t* __restrict__ out) {
+    __shared__ uint8_t flags[KD_GEN_ALLOWED_MAX];
+    __shared__ float sv[16];
+    __shared__ int si[16];
+    const int b = blockIdx.x;
+    int64_t* seq = seq_all + (size_t)b * smax;
+    const bf16* scores = scores_all + (size_t)b * lds;
+    const int len = max(0, min(cur_dev[b], smax));   // the ids read never leave the row
+    gen_flags_ids(ids, A, seq, len, penalty, ngram, flags);
     float best = -INFINITY;
     int bj = 0x7fffffff;
     for (int j = threadIdx.x; j < A; j += blockDim.x) {
-        float s = (float)scores[j];
-        const uint32_t f = flags[j];
-        if (f & 1) s = s < 0.f ? __fmul_rn(s, penalty) : __fdiv_rn(s, penalty);
-        if (f & 2) s = -INFINITY;
+        const float s = gen_processed((float)scores[j], flags[j], penalty);
         if (s > best || (s == best && j < bj)) { best = s; bj = j; }   // NaN never wins
     }
 #pragma unroll
@@ -1098,6 +1121,375 @@ __global__ void __launch_bounds__(1024) k_gen_select_ids(const bf16* __restrict_
         if (len < smax) seq[len] = tok;
         if (out) out[b] = tok;
         cur_dev[b] = len + 1;
+    }
+}
+
+// --------------------------------------------------------------- sampling (do_sample=True) ----
+// k_gen_sample draws row b = blockIdx.x's token from the processed scores of the select kernels
+// (their flag passes and gen_processed), then temperature, top-k, top-p and one Philox draw
+// (include/kdstep.h states the semantics).  One workgroup of 1024 threads owns the row, so the
+// grid is the batch and nothing a row computes can depend on nb or on its slot.  Every sum is an
+// integer sum: a weight exp(t - max) becomes floor(w * 2^40) once (N <= 2^18 of them stay below
+// 2^58), so Z, the top-p masses and the cumulative walk are exact in any order, and the 8-bit
+// radix-select histograms are integer LDS atomics (GS_COPIES padded copies, chosen by the lane:
+// logits crowd into a few exponent bins, and one copy would serialise the wave on them).
+// Passes over the row, which stays in the workspace (t fp32, q = fixed-point weights, 256-id tile sums):
+//   1  processed scores / T -> t, the row maximum, the top-k count histogram of the keys' top byte
+//   2-4  (top-k)  the next three bytes of the k-th largest key, over the entries under its prefix
+//   5  q for the entries top-k kept, Z, the top-p mass histogram of the top byte
+//   6-8  (top-p)  the next three bytes of the cut's key (masses of the entries under its prefix)
+//   9  tile sums of the kept q; the tile, then the id inside it, that the draw's target falls in
+constexpr int GS_TILE = 256;     // ids per tile sum: 64 lanes x 4
+constexpr int GS_COPIES = 16;    // histogram copies
+constexpr int GS_HLD = 257;      // 64-bit words per copy: copy c of a bin sits c banks (of 8 B) further
+typedef unsigned long long u64;
+typedef __attribute__((ext_vector_type(2))) unsigned long long u64x2;
+
+struct GsLayout {   // one row's workspace: every part 16-byte aligned
+    size_t npad, tiles, q_off, tsum_off, t_off, flags_off, row_bytes;
+};
+__host__ __device__ inline GsLayout gs_layout(int N) {
+    GsLayout l;
+    l.npad = ((size_t)N + GS_TILE - 1) / GS_TILE * GS_TILE;
+    l.tiles = l.npad / GS_TILE;
+    l.q_off = 0;
+    l.tsum_off = l.npad * 8;
+    l.t_off = l.tsum_off + (l.tiles + 1) / 2 * 16;
+    l.flags_off = l.t_off + l.npad * 4;
+    l.row_bytes = (l.flags_off + l.npad + 255) / 256 * 256;
+    return l;
+}
+
+// Order-preserving key of a float that is not NaN (-inf lowest).
+__device__ __forceinline__ uint32_t gs_key(float t) {
+    const uint32_t b = __float_as_uint(t);
+    return (b & 0x80000000u) ? ~b : (b | 0x80000000u);
+}
+
+// Word 0 of Philox4x32-10 at counter (c0, stream lo, stream hi, 0) under key (seed lo, seed hi).
+__device__ __forceinline__ uint32_t gs_philox(uint64_t seed, uint32_t c0, uint64_t stream) {
+    uint32_t k0 = (uint32_t)seed, k1 = (uint32_t)(seed >> 32);
+    uint32_t c1 = (uint32_t)stream, c2 = (uint32_t)(stream >> 32), c3 = 0u;
+#pragma unroll
+    for (int r = 0; r < 10; ++r) {
+        const uint32_t h0 = __umulhi(0xD2511F53u, c0), l0 = 0xD2511F53u * c0;
+        const uint32_t h1 = __umulhi(0xCD9E8D57u, c2), l1 = 0xCD9E8D57u * c2;
+        c0 = h1 ^ c1 ^ k0;
+        c1 = l1;
+        c2 = h0 ^ c3 ^ k1;
+        c3 = l0;
+        k0 += 0x9E3779B9u;
+        k1 += 0xBB67AE85u;
+    }
+    return c0;
+}
+
+__device__ __forceinline__ u64 gs_wave_sum(u64 v) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+    return v;
+}
+__device__ __forceinline__ u64 gs_wave_scan(u64 v) {   // inclusive, ascending lanes
+    const int lane = threadIdx.x & 63;
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) {
+        const u64 n = __shfl_up(v, o, 64);
+        if (lane >= o) v += n;
+    }
+    return v;
+}
+__device__ __forceinline__ void gs_hist_clear(u64* hist) {
+    for (int i = threadIdx.x; i < GS_COPIES * GS_HLD; i += blockDim.x) hist[i] = 0;
+    __syncthreads();
+}
+__device__ __forceinline__ void gs_hist_add(u64* hist, uint32_t digit, u64 v) {
+    atomicAdd(&hist[(threadIdx.x & (GS_COPIES - 1)) * GS_HLD + digit], v);
+}
+
+// f(i4, t[4 * i4 .. 4 * i4 + 3]) over the row, four 16-byte loads per thread in flight: one workgroup
+// reads the whole row, and with one load per thread a pass waits for 150 round trips in a row.
+// The trip count is the workgroup's, and i4 < nvec is wave-uniform (nvec is a multiple of 64).
+constexpr int GS_UNROLL = 4;
+template <typename F>
+__device__ __forceinline__ void gs_for_each4(const float* __restrict__ t, int npad, F f) {
+    const int nvec = npad / 4, nt = blockDim.x;
+    for (int base = threadIdx.x; base < nvec; base += GS_UNROLL * nt) {
+        f32x4 tv[GS_UNROLL];
+#pragma unroll
+        for (int k = 0; k < GS_UNROLL; ++k) tv[k] = ((const f32x4*)t)[min(base + k * nt, nvec - 1)];
+#pragma unroll
+        for (int k = 0; k < GS_UNROLL; ++k)
+            if (base + k * nt < nvec) f(base + k * nt, tv[k]);
+    }
+}
+
+// Radix select, most significant byte first, over the keys of t [npad]: the largest key K such
+// that the entries with a key >= K weigh at least `target` (an entry weighs 1, or its q with
+// MASS); `kept` = what they weigh.  That is the k-th largest key (target = k), and with masses the
+// smallest key whose strictly larger entries weigh less than target (the top-p cut).  The caller
+// has filled hist with the first byte's histogram; the other three bytes take one pass each over
+// the entries under the prefix found so far.  A target above the whole weight selects the lowest
+// occupied key.  Every thread returns the same values.
+template <bool MASS>
+__device__ __forceinline__ uint32_t gs_radix_select(const float* __restrict__ t, const u64* __restrict__ q, int npad,
+                                                    u64 target, u64* hist, u64* tot, u64* sel, u64& kept) {
+    uint32_t prefix = 0;
+    u64 above = 0;   // weight of the entries above the prefix
+    for (int level = 0; level < 4; ++level) {
+        const int shift = 24 - 8 * level;
+        if (level > 0) {
+            gs_hist_clear(hist);
+            gs_for_each4(t, npad, [&](int i4, const f32x4& tv) {
+#pragma unroll
+                for (int e = 0; e < 4; ++e) {
+                    const uint32_t key = gs_key(tv[e]);
+                    if ((key >> (shift + 8)) != prefix) continue;
+                    const u64 v = MASS ? q[i4 * 4 + e] : 1ull;
+                    if (v) gs_hist_add(hist, (key >> shift) & 255u, v);
+                }
+            });
+        }
+        __syncthreads();
+        if (threadIdx.x < 256) {
+            u64 s = 0;
+#pragma unroll
+            for (int c = 0; c < GS_COPIES; ++c) s += hist[c * GS_HLD + threadIdx.x];
+            tot[threadIdx.x] = s;
+        }
+        __syncthreads();
+        if (threadIdx.x < 64) {   // lane l: bins 255 - 4l ... 252 - 4l, the largest first
+            const int lane = threadIdx.x;
+            u64 v[4], ls = 0;
+#pragma unroll
+            for (int e = 0; e < 4; ++e) {
+                v[e] = tot[255 - 4 * lane - e];
+                ls += v[e];
+            }
+            const u64 incl = gs_wave_scan(ls), total = __shfl(incl, 63, 64);
+            const u64 want = target < total ? target : total;
+            u64 run = incl - ls;
+            if (total == 0) {
+                if (lane == 0) { sel[0] = 0; sel[1] = 1; sel[2] = above; sel[3] = 0; }
+            } else if (run < want && incl >= want) {   // one lane: incl never decreases
+#pragma unroll
+                for (int e = 0; e < 4; ++e) {
+                    if (run < want && run + v[e] >= want) {
+                        sel[0] = 255 - 4 * lane - e;
+                        sel[1] = want - run;
+                        sel[2] = above + run;
+                        sel[3] = v[e];
+                    }
+                    run += v[e];
+                }
+            }
+        }
+        __syncthreads();
+        prefix = (prefix << 8) | (uint32_t)sel[0];
+        target = sel[1];
+        above = sel[2];
+        kept = above + sel[3];
+        __syncthreads();   // sel and hist are rewritten by the next level
+    }
+    return prefix;
+}
+
+template <bool IDS>
+__global__ void __launch_bounds__(1024) k_gen_sample(const bf16* __restrict__ scores_all, int64_t lds, int N,
+                                                     const int* __restrict__ ids, int64_t* __restrict__ seq_all,
+                                                     int smax, int* __restrict__ cur_dev, float penalty, int ngram,
+                                                     float temperature, int top_k, float top_p, uint64_t seed,
+                                                     const int64_t* __restrict__ streams, unsigned char* __restrict__ ws,
+                                                     int64_t* __restrict__ out, float* __restrict__ u_out) {
+    __shared__ u64 hist[GS_COPIES * GS_HLD];
+    __shared__ u64 tot[256];
+    __shared__ u64 sel[4];
+    __shared__ u64 wsum[16];
+    __shared__ float red[16];
+    __shared__ __attribute__((aligned(16))) uint8_t flags_s[IDS ? KD_GEN_ALLOWED_MAX : 16];
+    const int b = blockIdx.x, lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+    const GsLayout lay = gs_layout(N);
+    const int npad = (int)lay.npad;
+    unsigned char* row = ws + (size_t)b * lay.row_bytes;
+    u64* q = (u64*)(row + lay.q_off);
+    u64* tsum = (u64*)(row + lay.tsum_off);
+    float* t = (float*)(row + lay.t_off);
+    uint8_t* flags = IDS ? flags_s : row + lay.flags_off;
+    int64_t* seq = seq_all + (size_t)b * smax;
+    const bf16* scores = scores_all + (size_t)b * lds;
+    const int len = max(0, min(cur_dev[b], smax));   // the ids read never leave the row
+    if constexpr (IDS) gen_flags_ids(ids, N, seq, len, penalty, ngram, flags);
+    else gen_flags_row(N, seq, len, penalty, ngram, flags);
+
+    // ---- pass 1
+    const bool use_k = top_k >= 1 && top_k < N;
+    if (use_k) gs_hist_clear(hist);
+    float mx = -INFINITY;
+    auto first = [&](float s, uint32_t f) {
+        float v = __fdiv_rn(gen_processed(s, f, penalty), temperature);
+        if (!(v == v)) v = -INFINITY;   // NaN is never chosen
+        if (v == 0.f) v = 0.f;          // -0 and +0 tie: one key
+        mx = fmaxf(mx, v);
+        if (use_k) gs_hist_add(hist, gs_key(v) >> 24, 1ull);
+        return v;
+    };
+    const int v8 = (((uintptr_t)scores & 15) == 0 && ((uintptr_t)flags & 7) == 0) ? N >> 3 : 0;
+    for (int base = threadIdx.x; base < v8; base += GS_UNROLL * blockDim.x) {
+        bf16x8 lv[GS_UNROLL];
+        u32x2 fv[GS_UNROLL];
+#pragma unroll
+        for (int k = 0; k < GS_UNROLL; ++k) {
+            const int c = min(base + k * (int)blockDim.x, v8 - 1);
+            lv[k] = ((const bf16x8*)scores)[c];
+            fv[k] = ((const u32x2*)flags)[c];
+        }
+#pragma unroll
+        for (int k = 0; k < GS_UNROLL; ++k) {
+            const int c = base + k * (int)blockDim.x;
+            if (c >= v8) continue;
+            f32x4 lo, hi;
+#pragma unroll
+            for (int e = 0; e < 4; ++e) {
+                lo[e] = first((float)lv[k][e], (fv[k].x >> (8 * e)) & 255u);
+                hi[e] = first((float)lv[k][4 + e], (fv[k].y >> (8 * e)) & 255u);
+            }
+            ((f32x4*)t)[2 * c] = lo;
+            ((f32x4*)t)[2 * c + 1] = hi;
+        }
+    }
+    for (int i = (v8 << 3) + threadIdx.x; i < N; i += blockDim.x) t[i] = first((float)scores[i], flags[i]);
+    for (int i = N + threadIdx.x; i < npad; i += blockDim.x) {   // the padding: -inf, weight 0
+        t[i] = -INFINITY;
+        if (use_k) gs_hist_add(hist, gs_key(-INFINITY) >> 24, 1ull);
+    }
+    mx = block_max<16>(mx, red);   // its barriers publish t and hist to the workgroup
+
+    // u: Philox at the position the token is written to
+    const uint32_t m24 = gs_philox(seed, (uint32_t)len, (uint64_t)streams[b]) >> 8;
+    int64_t token = 0;
+    if (mx > -INFINITY) {   // else no score above -inf: token 0, the greedy kernels' rule
+        u64 kept = 0;
+        uint32_t thr = 0;
+        if (use_k) thr = gs_radix_select<false>(t, q, npad, (u64)top_k, hist, tot, sel, kept);
+
+        // ---- pass 5: the fixed-point weights of what top-k kept
+        const bool use_p = top_p < 1.0f;
+        if (use_p) gs_hist_clear(hist);
+        u64 z = 0;
+        gs_for_each4(t, npad, [&](int i4, const f32x4& tv) {
+            u64 qv[4];
+#pragma unroll
+            for (int e = 0; e < 4; ++e) {
+                const uint32_t key = gs_key(tv[e]);
+                qv[e] = 0ull;
+                if (key >= thr) {   // few entries behind a top-k: the exp is theirs alone
+                    const float w = tv[e] == mx ? 1.0f : expf(tv[e] - mx);
+                    qv[e] = (u64)(w * 1099511627776.0f);
+                }
+                z += qv[e];
+                if (use_p && qv[e]) gs_hist_add(hist, key >> 24, qv[e]);
+            }
+            ((u64x2*)q)[2 * i4] = u64x2{qv[0], qv[1]};
+            ((u64x2*)q)[2 * i4 + 1] = u64x2{qv[2], qv[3]};
+        });
+        z = gs_wave_sum(z);
+        if (lane == 0) wsum[wv] = z;
+        __syncthreads();   // also publishes q and hist
+        z = 0;
+#pragma unroll
+        for (int i = 0; i < 16; ++i) z += wsum[i];
+        if (use_p) {
+            // keep j iff the mass strictly above it is < top_p * Z, i.e. < ceil(top_p * Z)
+            const double pd = ceil((double)top_p * (double)z);
+            u64 target = (u64)pd;
+            target = target < 1 ? 1 : (target > z ? z : target);
+            thr = gs_radix_select<true>(t, q, npad, target, hist, tot, sel, z);
+        }
+        __syncthreads();   // wsum is reused below
+
+        // ---- pass 9: tile sums of the kept weights, then the tile and the id of the draw
+        {
+            const int nvec = npad / 4, nt = blockDim.x;
+            for (int base = threadIdx.x; base < nvec; base += GS_UNROLL * nt) {
+                f32x4 tv[GS_UNROLL];
+                u64x2 qa[GS_UNROLL], qb[GS_UNROLL];
+#pragma unroll
+                for (int k = 0; k < GS_UNROLL; ++k) {
+                    const int i4 = min(base + k * nt, nvec - 1);
+                    tv[k] = ((const f32x4*)t)[i4];
+                    qa[k] = ((const u64x2*)q)[2 * i4];
+                    qb[k] = ((const u64x2*)q)[2 * i4 + 1];
+                }
+#pragma unroll
+                for (int k = 0; k < GS_UNROLL; ++k) {
+                    const int i4 = base + k * nt;
+                    if (i4 >= nvec) continue;   // wave-uniform
+                    u64 s = 0;
+                    s += gs_key(tv[k][0]) >= thr ? qa[k].x : 0ull;
+                    s += gs_key(tv[k][1]) >= thr ? qa[k].y : 0ull;
+                    s += gs_key(tv[k][2]) >= thr ? qb[k].x : 0ull;
+                    s += gs_key(tv[k][3]) >= thr ? qb[k].y : 0ull;
+                    s = gs_wave_sum(s);
+                    if (lane == 0) tsum[i4 >> 6] = s;
+                }
+            }
+        }
+        if (threadIdx.x == 0) sel[0] = sel[1] = sel[2] = 0;   // Z > 0 (the maximum is kept), so all three are set below
+        __syncthreads();
+        // smallest j with C_j > u * Z  <=>  C_j > floor(m24 * Z / 2^24); Z is the kept weight, C_last = Z
+        const u64 target = (__umul64hi((u64)m24, z) << 40) | (((u64)m24 * z) >> 24);
+        const int tiles = npad / GS_TILE;
+        u64 base = 0;
+        for (int c0 = 0; c0 < tiles; c0 += 1024) {
+            const int ti = c0 + threadIdx.x;
+            const u64 v = ti < tiles ? tsum[ti] : 0ull;
+            const u64 incl = gs_wave_scan(v);
+            if (lane == 63) wsum[wv] = incl;
+            __syncthreads();
+            u64 off = base, all = 0;
+#pragma unroll
+            for (int i = 0; i < 16; ++i) {
+                if (i < wv) off += wsum[i];
+                all += wsum[i];
+            }
+            const u64 cj = off + incl;
+            if (cj > target && cj - v <= target) {   // one thread of one chunk: cj never decreases
+                sel[0] = (u64)ti;
+                sel[1] = cj - v;
+            }
+            base += all;
+            __syncthreads();
+        }
+        if (wv == 0) {
+            const int i4 = (int)sel[0] * 64 + lane;
+            const f32x4 tv = ((const f32x4*)t)[i4];
+            const u64x2 qa = ((const u64x2*)q)[2 * i4], qb = ((const u64x2*)q)[2 * i4 + 1];
+            u64 qv[4] = {qa.x, qa.y, qb.x, qb.y}, s = 0;
+#pragma unroll
+            for (int e = 0; e < 4; ++e) {
+                if (gs_key(tv[e]) < thr) qv[e] = 0;
+                s += qv[e];
+            }
+            const u64 incl = sel[1] + gs_wave_scan(s);
+            if (incl > target && incl - s <= target) {
+                u64 run = incl - s;
+                int j = i4 * 4;
+#pragma unroll
+                for (int e = 0; e < 4; ++e) {
+                    if (run <= target && run + qv[e] > target) j = i4 * 4 + e;
+                    run += qv[e];
+                }
+                sel[2] = (u64)j;
+            }
+        }
+        __syncthreads();
+        const int j = (int)sel[2];
+        token = IDS ? (int64_t)ids[j] : (int64_t)j;
+    }
+    if (threadIdx.x == 0) {
+        if (len < smax) seq[len] = token;
+        out[b] = token;
+        cur_dev[b] = len + 1;
+        if (u_out) u_out[b] = (float)m24 * 5.9604644775390625e-08f;
     }
 }
 
@@ -1473,6 +1865,38 @@ int launch_gen_select_ids(const void* scores, int64_t lds, const int* ids, int A
     hipLaunchKernelGGL(k_gen_select_ids, dim3(nb), dim3(1024), 0, as_stream(stream), (const bf16*)scores, lds, ids, A, seq,
                        smax, cur_dev, penalty, ngram, out);
     KD_LAUNCH_CHECK("k_gen_select_ids");
+    return KD_OK;
+}
+
+constexpr int GS_N_MAX = 1 << 18;   // 2^18 weights of at most 2^40 each: every sum below 2^58
+
+size_t gen_sample_ws(int nb, int N) {
+    if (nb < 1 || N < 1 || N > GS_N_MAX) return 0;
+    return (size_t)nb * gs_layout(N).row_bytes;
+}
+
+int launch_gen_sample(const void* scores, int64_t lds, int N, const int* ids, int64_t* seq, int smax, int nb,
+                      int* cur_dev, float penalty, int ngram, float temperature, int top_k, float top_p, uint64_t seed,
+                      const int64_t* streams, void* ws, size_t ws_bytes, int64_t* out, float* u_out, void* stream) {
+    KD_CHECK_ARG(scores && seq && cur_dev && streams && ws && out, "gen_sample: null pointer");
+    KD_CHECK_ARG(penalty > 0.f && ngram >= 0, "gen_sample: penalty must be > 0 and ngram >= 0");
+    KD_CHECK_ARG(std::isfinite(temperature) && temperature > 0.f, "gen_sample: temperature must be finite and > 0");
+    KD_CHECK_ARG(top_k >= 0, "gen_sample: top_k must be >= 0");
+    KD_CHECK_ARG(top_p > 0.f && top_p <= 1.0f, "gen_sample: top_p must lie in (0, 1]");
+    KD_CHECK_SHAPE(N >= 1 && N <= (ids ? KD_GEN_ALLOWED_MAX : GS_N_MAX) && smax > 0 && lds >= N && nb >= 1 &&
+                       nb <= GB_ROWS,
+                   "gen_sample: 1 <= N <= 262144 (with ids: KD_GEN_ALLOWED_MAX), smax positive, ld >= N, 1 <= nb <= 16");
+    KD_CHECK_SHAPE(ws_bytes >= gen_sample_ws(nb, N), "gen_sample: workspace smaller than kd_gen_sample_workspace_size");
+    KD_CHECK_SHAPE(((uintptr_t)ws & 15) == 0, "gen_sample: workspace must be 16-byte aligned");
+    if (ids)
+        hipLaunchKernelGGL(k_gen_sample<true>, dim3(nb), dim3(1024), 0, as_stream(stream), (const bf16*)scores, lds, N,
+                           ids, seq, smax, cur_dev, penalty, ngram, temperature, top_k, top_p, seed, streams,
+                           (unsigned char*)ws, out, u_out);
+    else
+        hipLaunchKernelGGL(k_gen_sample<false>, dim3(nb), dim3(1024), 0, as_stream(stream), (const bf16*)scores, lds, N,
+                           (const int*)nullptr, seq, smax, cur_dev, penalty, ngram, temperature, top_k, top_p, seed,
+                           streams, (unsigned char*)ws, out, u_out);
+    KD_LAUNCH_CHECK("k_gen_sample");
     return KD_OK;
 }
 

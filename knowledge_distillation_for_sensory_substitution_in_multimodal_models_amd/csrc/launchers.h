@@ -106,6 +106,10 @@ int launch_gemv_batch_gather(const void* x, int64_t ldx, int nb, const void* W, 
                              void* y, int N_full, int K, void* stream);
 int launch_gen_select_ids(const void* scores, int64_t lds, const int* ids, int A, int64_t* seq, int smax, int nb,
                           int* cur_dev, float penalty, int ngram, int64_t* out, void* stream);
+size_t gen_sample_ws(int nb, int N);
+int launch_gen_sample(const void* scores, int64_t lds, int N, const int* ids, int64_t* seq, int smax, int nb,
+                      int* cur_dev, float penalty, int ngram, float temperature, int top_k, float top_p, uint64_t seed,
+                      const int64_t* streams, void* ws, size_t ws_bytes, int64_t* out, float* u_out, void* stream);
 int launch_image_resize(const uint8_t* in, int H, int W, uint8_t* out, int oh, int ow, void* ws, size_t ws_bytes,
                         void* stream);
 int launch_anyres_tiles(const uint8_t* base, const uint8_t* resized, int nh, int nw, int bh, int bw, int patch,

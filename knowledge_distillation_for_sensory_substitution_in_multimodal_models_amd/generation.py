@@ -7,7 +7,7 @@ Drop-in for the call the reference's evaluation makes on the trained student
                    repetition_penalty=1.2, no_repeat_ngram_size=2, temperature=0.7)
 
 `do_sample` is not set there, so decoding is greedy and `temperature` has no effect (transformers
-only applies it when sampling).  The prompt runs through the same forward as training
+only applies it when sampling; with do_sample=True see "Sampling" below).  The prompt runs through the same forward as training
 (LlavaOnevisionModel.forward: SigLIP, projector, anyres pack, Qwen2), whose roped keys and values
 seed a per-layer KV cache [HKV, L + max_new_tokens, hd]; each new token then runs one row through
 every layer (kd_gemv with the RMSNorms fused in front and bias / residual / SwiGLU epilogues, kd_qkv_split with its
@@ -56,6 +56,36 @@ gathered head behind its extend pass).  A decode step reads only the A allowed r
 entry, sequence tokens found by binary search) where ops.gemv_gather_supported(vocab, hidden) holds;
 elsewhere, or with restrict_head=False, it runs the full head and takes the allowed columns: the
 same bits either way.  restrict_head=True raises ValueError where the gathered head does not exist.
+
+Sampling.  do_sample=True (default False: the greedy call, launch for launch; temperature, top_k,
+top_p, seed and sample_streams are then ignored, as transformers ignores its warpers) draws every
+token of a row with kd_gen_sample in place of the select: the prefill's token, the token behind
+generate_grouped()'s extend pass and every decode step inside the captured graph, behind the same
+gathered head or full-head columns when allowed_token_ids is given.  It is transformers' _sample
+made reproducible.  Per row and step:
+  1. the processed fp32 scores of the greedy kernels: repetition penalty, n-gram ban, and with
+     allowed_token_ids every other id at -inf;
+  2. t = s / temperature in fp32 (None: 1.0; must be > 0);
+  3. top_k >= 1 keeps every entry with t >= the k-th largest t, ties at that value included, as
+     TopKLogitsWarper; top_k >= the row's width keeps everything, 0 is off;
+  4. top_p < 1: with p = softmax(t) over what top-k kept, an entry is kept iff the entries with a
+     strictly larger score have mass < top_p.  That is TopPLogitsWarper's set whenever no two scores
+     at the cut are exactly equal; equal scores are kept or dropped together here, where
+     transformers' result depends on its sort order.  The largest entry is always kept;
+  5. w = exp(t - max t) on what is kept, Z = sum w, and the token is the smallest id whose inclusive
+     cumulative weight (ascending ids) exceeds u * Z; an entry of weight 0 (dropped, banned, -inf,
+     NaN) is never chosen, and a row without a score above -inf gives token 0;
+  6. u = (x >> 8) * 2^-24 with x the first word of Philox4x32-10 under key (seed & 0xffffffff,
+     seed >> 32) at counter (pos, stream & 0xffffffff, stream >> 32, 0): pos is the index in the
+     row's sequence the token is written to, stream the row's entry of sample_streams.
+So a row's tokens are a function of its prompt, the decode settings, seed and its own stream: not of
+the batch it sits in, its slot, the chunking, graph, stop_check_every or the head taken.  seed: an
+int in [0, 2^64); None draws one from torch's default CPU generator (torch.manual_seed governs it)
+and stats["seed"] reports it.  sample_streams: one int in [0, 2^63) per prompt (generate(): one int
+or a one-element sequence); the default is the prompt's index in the call (generate_grouped(): in
+the flattened question order; generate(): 0), so row r alone with sample_streams=[r] reproduces row
+r of the batch.  A bad temperature, top_k, top_p, seed or sample_streams raises ValueError before any
+device work.  return_logits gives the raw rows, as in the greedy call.
 """
 from __future__ import annotations
 
@@ -201,6 +231,69 @@ def _allowed(model, allowed_token_ids, restrict_head, who: str):
     return _Allowed(model, allowed_token_ids, restrict_head, who)
 
 
+class _Sampler:
+    """The sampling settings of one call (do_sample=True), validated once, before any device work:
+    temperature, top_k, top_p, the seed and one Philox stream id per prompt of the call.  rows(lo, hi)
+    is the part of a chunk: its stream ids on the device, fixed for the captured step."""
+
+    def __init__(self, temperature, top_k, top_p, seed, sample_streams, n_rows: int, who: str):
+        import math
+        import numbers
+        t = 1.0 if temperature is None else temperature
+        if isinstance(t, bool) or not isinstance(t, numbers.Real) or not math.isfinite(t) or t <= 0:
+            raise ValueError(f"{who}: temperature must be a finite number > 0, got {temperature!r}")
+        if isinstance(top_k, bool) or not isinstance(top_k, numbers.Integral) or top_k < 0:
+            raise ValueError(f"{who}: top_k must be an int >= 0 (0: off), got {top_k!r}")
+        if isinstance(top_p, bool) or not isinstance(top_p, numbers.Real) or not 0.0 < top_p <= 1.0:
+            raise ValueError(f"{who}: top_p must lie in (0, 1], got {top_p!r}")
+        if seed is not None and (isinstance(seed, bool) or not isinstance(seed, numbers.Integral)
+                                 or not 0 <= seed < 1 << 64):
+            raise ValueError(f"{who}: seed must be an int in [0, 2^64) or None, got {seed!r}")
+        if sample_streams is None:
+            streams = list(range(n_rows))
+        else:
+            streams = [sample_streams] if isinstance(sample_streams, numbers.Integral) else list(sample_streams)
+            if len(streams) != n_rows:
+                raise ValueError(f"{who}: sample_streams must hold one stream id per prompt ({n_rows}), "
+                                 f"got {len(streams)}")
+            for v in streams:
+                if isinstance(v, bool) or not isinstance(v, numbers.Integral) or not 0 <= v < 1 << 63:
+                    raise ValueError(f"{who}: every sample_streams entry must be an int in [0, 2^63), got {v!r}")
+        if seed is None:   # torch's default CPU generator: torch.manual_seed governs it
+            lo, hi = torch.randint(0, 1 << 32, (2,), dtype=torch.int64).tolist()
+            seed = hi << 32 | lo
+        self.temperature, self.top_k, self.top_p = float(t), min(int(top_k), 2 ** 31 - 1), float(top_p)
+        self.seed, self.streams = int(seed), [int(v) for v in streams]
+
+    def rows(self, dev, lo: int, hi: int):
+        return _SamplerRows(self, torch.tensor(self.streams[lo:hi], dtype=torch.int64, device=dev))
+
+
+class _SamplerRows:
+    def __init__(self, s: _Sampler, streams):
+        self.s, self.streams = s, streams
+
+    def draw(self, allowed, scores, seq, cur, repetition_penalty, no_repeat_ngram_size, out=None, row=None):
+        """kd_gen_sample in place of the select of the same scores: over all rows of the chunk, or
+        (row = b: scores [1, N], seq [1, smax], cur [1]) with row b's stream."""
+        s = self.s
+        streams = self.streams if row is None else self.streams[row:row + 1]
+        ops.gen_sample(scores, seq, cur, ids=None if allowed is None else allowed.ids,
+                       repetition_penalty=repetition_penalty, no_repeat_ngram_size=no_repeat_ngram_size,
+                       temperature=s.temperature, top_k=s.top_k, top_p=s.top_p, seed=s.seed, streams=streams, out=out)
+
+
+def _sampler(do_sample, temperature, top_k, top_p, seed, sample_streams, n_rows: int, stats, who: str):
+    """None for the greedy call (temperature, top_k, top_p, seed and sample_streams are then ignored,
+    as transformers ignores its warpers when not sampling)."""
+    if not do_sample:
+        return None
+    s = _Sampler(temperature, top_k, top_p, seed, sample_streams, n_rows, who)
+    if stats is not None:
+        stats["seed"] = s.seed
+    return s
+
+
 def _decode_layers(model):
     """Per layer: (input norm, q|k|v weight, q|k|v bias, o_proj, post-attention norm, gate|up, down)."""
     T, P = model.cfg.text, model.P
@@ -264,9 +357,12 @@ def generate(model, input_ids: torch.Tensor, pixel_values: torch.Tensor, image_s
              repetition_penalty: float = 1.0, no_repeat_ngram_size: int = 0, eos_token_id=EOS_TOKEN_IDS,
              pad_token_id: int | None = None, temperature: float | None = None, return_logits: bool = False,
              graph: bool = True, fuse_norm: bool | None = None, stop_check_every: int | None = None,
-             stats: dict | None = None, allowed_token_ids=None, restrict_head: bool | None = None):
+             stats: dict | None = None, allowed_token_ids=None, restrict_head: bool | None = None,
+             do_sample: bool = False, top_k: int = 0, top_p: float = 1.0, seed: int | None = None,
+             sample_streams=None):
     """-> int64 [1, L + n_new] on the device (and the bf16 logits row of every step if
-    return_logits).  `temperature` is accepted for signature parity and ignored (greedy).
+    return_logits).  Greedy unless do_sample (module docstring, "Sampling": temperature, top_k, top_p,
+    seed and sample_streams, one int here, then take effect; stats also receives "seed").
     fuse_norm: RMSNorm fused into the q|k|v and gate|up GEMVs (default: FUSE_NORM_DEFAULT).
     stop_check_every = k (default STOP_CHECK_EVERY; 0: never): with 1..KD_GEN_EOS_MAX EOS ids the
     loop asks the device every k steps whether the row has emitted one and then ends, after
@@ -276,10 +372,11 @@ def generate(model, input_ids: torch.Tensor, pixel_values: torch.Tensor, image_s
     ([length at the first EOS, or 0]).
     allowed_token_ids, restrict_head: constrained decoding, see the module docstring (the logits
     returned are then the compact rows [1, A])."""
-    del temperature, pad_token_id   # greedy, batch of one: no padding of finished rows
+    del pad_token_id   # batch of one: no padding of finished rows
     k_stop = _stop_every(stop_check_every, "generate")
     allowed = _allowed(model, allowed_token_ids, restrict_head, "generate")
     _stats_begin(stats)
+    sampler = _sampler(do_sample, temperature, top_k, top_p, seed, sample_streams, 1, stats, "generate")
     FUSE_NORM = FUSE_NORM_DEFAULT if fuse_norm is None else bool(fuse_norm)
     if input_ids.dim() != 2 or input_ids.shape[0] != 1:
         raise ValueError("generate: batch size 1 (as evaluate_onevision.py runs it)")
@@ -304,10 +401,15 @@ def generate(model, input_ids: torch.Tensor, pixel_values: torch.Tensor, image_s
     seq[:L].copy_(input_ids[0])
     logits = model.logits(fwd["hn"][L - 1:L])
     del fwd
-    if allowed is None:
+    samp = None if sampler is None else sampler.rows(dev, 0, 1)
+    if allowed is not None:
+        logits = allowed.columns(logits)
+    if samp is not None:
+        samp.draw(allowed, logits, seq.view(1, smax), torch.full((1,), L, dtype=torch.int32, device=dev),
+                  repetition_penalty, no_repeat_ngram_size)
+    elif allowed is None:
         ops.gen_select(logits, seq, L, repetition_penalty, no_repeat_ngram_size)
     else:
-        logits = allowed.columns(logits)
         allowed.select(logits, seq.view(1, smax), torch.full((1,), L, dtype=torch.int32, device=dev),
                        repetition_penalty, no_repeat_ngram_size)
     steps = [logits] if return_logits else None
@@ -349,9 +451,13 @@ def generate(model, input_ids: torch.Tensor, pixel_values: torch.Tensor, image_s
         hn, _, _ = ops.norm_fwd(x, P[lp + "norm.weight"], None, T.eps, rms=True, save_stats=False)
         if allowed is None:
             lg = ops.gemv(hn, model.lm_head_weight())
-            ops.gen_select(lg, seq, 0, repetition_penalty, no_repeat_ngram_size, out=tok, cur=cur)
         else:
             lg = allowed.head(hn, model.lm_head_weight(), batch=False)
+        if samp is not None:
+            samp.draw(allowed, lg, seq.view(1, smax), cur, repetition_penalty, no_repeat_ngram_size, out=tok)
+        elif allowed is None:
+            ops.gen_select(lg, seq, 0, repetition_penalty, no_repeat_ngram_size, out=tok, cur=cur)
+        else:
             allowed.select(lg, seq.view(1, smax), cur, repetition_penalty, no_repeat_ngram_size, out=tok)
         stop.mark(tok, cur)
         return lg
@@ -375,7 +481,8 @@ def generate_batch(model, prompts, max_new_tokens: int = 32, repetition_penalty:
                    no_repeat_ngram_size: int = 0, eos_token_id=EOS_TOKEN_IDS, pad_token_id: int | None = None,
                    temperature: float | None = None, return_logits: bool = False, graph: bool = True,
                    stop_check_every: int | None = None, stats: dict | None = None, allowed_token_ids=None,
-                   restrict_head: bool | None = None):
+                   restrict_head: bool | None = None, do_sample: bool = False, top_k: int = 0, top_p: float = 1.0,
+                   seed: int | None = None, sample_streams=None):
     """generate() for several prompts at once: prompts is a sequence of (input_ids [1, L_i],
     pixel_values [1, P_i, 3, 384, 384], image_sizes [1, 2]), ragged in L_i and P_i (no padding, no
     attention mask) -> list of int64 [1, L_i + n_i] (and, with return_logits, a list per row of the
@@ -392,12 +499,16 @@ def generate_batch(model, prompts, max_new_tokens: int = 32, repetition_penalty:
     the last row's first EOS), so the results are the same bits for every k.  stats (a dict)
     receives, per chunk, steps_run, steps_max, checks and finished_at (per row the length at its
     first EOS, or 0).  allowed_token_ids, restrict_head: constrained decoding, see the module
-    docstring (the logits returned are then the compact rows [1, A])."""
-    del temperature, pad_token_id   # greedy; finished rows are cut, not padded
+    docstring (the logits returned are then the compact rows [1, A]).  do_sample, temperature, top_k,
+    top_p, seed, sample_streams (one stream id per prompt; default: its index): module docstring,
+    "Sampling"; a row's tokens depend on its prompt, the settings, seed and its own stream only."""
+    del pad_token_id   # finished rows are cut, not padded
     k_stop = _stop_every(stop_check_every, "generate_batch")
     allowed = _allowed(model, allowed_token_ids, restrict_head, "generate_batch")
     _stats_begin(stats)
     prompts = list(prompts)
+    sampler = _sampler(do_sample, temperature, top_k, top_p, seed, sample_streams, len(prompts), stats,
+                       "generate_batch")
     if not prompts:
         raise ValueError("generate_batch: no prompts")
     if int(max_new_tokens) < 1:
@@ -408,14 +519,15 @@ def generate_batch(model, prompts, max_new_tokens: int = 32, repetition_penalty:
     outs, logs = [], []
     for c0 in range(0, len(prompts), MAX_BATCH):
         o, lg = _generate_rows(model, prompts[c0:c0 + MAX_BATCH], int(max_new_tokens), repetition_penalty,
-                               no_repeat_ngram_size, eos_token_id, return_logits, graph, k_stop, stats, allowed)
+                               no_repeat_ngram_size, eos_token_id, return_logits, graph, k_stop, stats, allowed,
+                               None if sampler is None else sampler.rows(model.device, c0, c0 + MAX_BATCH))
         outs += o
         logs += lg
     return (outs, logs) if return_logits else outs
 
 
 def _generate_rows(model, prompts, max_new_tokens, repetition_penalty, no_repeat_ngram_size, eos_token_id,
-                   return_logits, graph, k_stop, stats, allowed):
+                   return_logits, graph, k_stop, stats, allowed, samp=None):
     T = model.cfg.text
     dev = model.device
     nb = len(prompts)
@@ -440,21 +552,25 @@ def _generate_rows(model, prompts, max_new_tokens, repetition_penalty, no_repeat
         seq[b, :L].copy_(input_ids[0])
         logits = model.logits(fwd["hn"][L - 1:L])
         del fwd
-        if allowed is None:
+        if allowed is not None:
+            logits = allowed.columns(logits)
+        if samp is not None:
+            samp.draw(allowed, logits, seq[b:b + 1], torch.full((1,), L, dtype=torch.int32, device=dev),
+                      repetition_penalty, no_repeat_ngram_size, row=b)
+        elif allowed is None:
             ops.gen_select(logits, seq[b], L, repetition_penalty, no_repeat_ngram_size)
         else:
-            logits = allowed.columns(logits)
             allowed.select(logits, seq[b:b + 1], torch.full((1,), L, dtype=torch.int32, device=dev),
                            repetition_penalty, no_repeat_ngram_size)
         if return_logits:
             steps[b].append(logits)
 
     return _decode_rows(model, kc, vc, seq, Ls, steps, max_new_tokens, repetition_penalty, no_repeat_ngram_size, eos,
-                        return_logits, graph, k_stop, stats, allowed)
+                        return_logits, graph, k_stop, stats, allowed, samp)
 
 
 def _decode_rows(model, kc, vc, seq, Ls, steps, max_new_tokens, repetition_penalty, no_repeat_ngram_size, eos,
-                 return_logits, graph, k_stop, stats, allowed=None):
+                 return_logits, graph, k_stop, stats, allowed=None, samp=None):
     """The batched decode loop behind generate_batch() and generate_grouped(): row b's caches hold
     its L_b prompt positions, seq[b, L_b] its first new token and steps[b] that token's logits row.
     The loop ends early once every row has emitted an EOS (_Stop)."""
@@ -488,9 +604,13 @@ def _decode_rows(model, kc, vc, seq, Ls, steps, max_new_tokens, repetition_penal
         hn, _, _ = ops.norm_fwd(x, P[lp + "norm.weight"], None, T.eps, rms=True, save_stats=False)
         if allowed is None:
             lg = ops.gemv_batch(hn, model.lm_head_weight())
-            ops.gen_select_batch(lg, seq, cur, repetition_penalty, no_repeat_ngram_size, out=tok)
         else:
             lg = allowed.head(hn, model.lm_head_weight(), batch=True)
+        if samp is not None:
+            samp.draw(allowed, lg, seq, cur, repetition_penalty, no_repeat_ngram_size, out=tok)
+        elif allowed is None:
+            ops.gen_select_batch(lg, seq, cur, repetition_penalty, no_repeat_ngram_size, out=tok)
+        else:
             allowed.select(lg, seq, cur, repetition_penalty, no_repeat_ngram_size, out=tok)
         stop.mark(tok, cur)
         return lg
@@ -517,7 +637,8 @@ def generate_grouped(model, groups, max_new_tokens: int = 32, repetition_penalty
                      no_repeat_ngram_size: int = 0, eos_token_id=EOS_TOKEN_IDS, pad_token_id: int | None = None,
                      temperature: float | None = None, return_logits: bool = False, graph: bool = True,
                      stop_check_every: int | None = None, stats: dict | None = None, allowed_token_ids=None,
-                     restrict_head: bool | None = None):
+                     restrict_head: bool | None = None, do_sample: bool = False, top_k: int = 0, top_p: float = 1.0,
+                     seed: int | None = None, sample_streams=None):
     """generate_batch() for questions grouped by image: groups is a sequence of (pixel_values
     [1, P, 3, 384, 384], image_sizes [1, 2], [input_ids [1, L_q], ...]) -> one list per group of int64
     [1, L_q + n_q] (and, with return_logits, the same nesting of per-step bf16 logits rows).
@@ -539,12 +660,17 @@ def generate_grouped(model, groups, max_new_tokens: int = 32, repetition_penalty
     stop_check_every and stats as in generate_batch(): a chunk of up to MAX_BATCH questions stops
     decoding once all of them have emitted an EOS (one stats entry per chunk).
     allowed_token_ids, restrict_head: constrained decoding, see the module docstring (the logits
-    returned are then the compact rows [1, A]; the head behind the extend pass is gathered too)."""
-    del temperature, pad_token_id   # greedy; finished rows are cut, not padded
+    returned are then the compact rows [1, A]; the head behind the extend pass is gathered too).
+    do_sample, temperature, top_k, top_p, seed, sample_streams: module docstring, "Sampling"; one
+    stream id per question in the flattened order of the groups (default: that index), and the token
+    behind the extend pass is drawn too."""
+    del pad_token_id   # finished rows are cut, not padded
     k_stop = _stop_every(stop_check_every, "generate_grouped")
     allowed = _allowed(model, allowed_token_ids, restrict_head, "generate_grouped")
     _stats_begin(stats)
     groups = [(px, sizes, list(qs)) for px, sizes, qs in groups]
+    sampler = _sampler(do_sample, temperature, top_k, top_p, seed, sample_streams, sum(len(qs) for _, _, qs in groups),
+                       stats, "generate_grouped")
     if not groups:
         raise ValueError("generate_grouped: no groups")
     if int(max_new_tokens) < 1:
@@ -577,7 +703,8 @@ def generate_grouped(model, groups, max_new_tokens: int = 32, repetition_penalty
         chunk = items[c0:c0 + MAX_BATCH]
         o, lg, carry = _generate_grouped_rows(model, chunk, carry, int(max_new_tokens), repetition_penalty,
                                               no_repeat_ngram_size, eos_token_id, return_logits, graph, k_stop,
-                                              stats, allowed)
+                                              stats, allowed,
+                                              None if sampler is None else sampler.rows(model.device, c0, c0 + MAX_BATCH))
         for (gi, *_), ob, lb in zip(chunk, o, lg if return_logits else [None] * len(o)):
             outs[gi].append(ob)
             logs[gi].append(lb)
@@ -585,7 +712,7 @@ def generate_grouped(model, groups, max_new_tokens: int = 32, repetition_penalty
 
 
 def _generate_grouped_rows(model, chunk, carry, max_new_tokens, repetition_penalty, no_repeat_ngram_size, eos_token_id,
-                           return_logits, graph, k_stop, stats, allowed):
+                           return_logits, graph, k_stop, stats, allowed, samp=None):
     T, P = model.cfg.text, model.P
     dev = model.device
     nb = len(chunk)
@@ -649,11 +776,15 @@ def _generate_grouped_rows(model, chunk, carry, max_new_tokens, repetition_penal
     cur = torch.tensor(Ls, dtype=torch.int32, device=dev)
     if allowed is None:
         lg = ops.gemv_batch(hn, model.lm_head_weight())
-        ops.gen_select_batch(lg, seq, cur, repetition_penalty, no_repeat_ngram_size)   # seq[b, L_b]; cur = L_b + 1
     else:
         lg = allowed.head(hn, model.lm_head_weight(), batch=True)
+    if samp is not None:
+        samp.draw(allowed, lg, seq, cur, repetition_penalty, no_repeat_ngram_size)   # seq[b, L_b]; cur = L_b + 1
+    elif allowed is None:
+        ops.gen_select_batch(lg, seq, cur, repetition_penalty, no_repeat_ngram_size)   # seq[b, L_b]; cur = L_b + 1
+    else:
         allowed.select(lg, seq, cur, repetition_penalty, no_repeat_ngram_size)
     steps = [[lg[b:b + 1]] if return_logits else [] for b in range(nb)]
     outs, steps = _decode_rows(model, kc, vc, seq, Ls, steps, max_new_tokens, repetition_penalty,
-                               no_repeat_ngram_size, eos, return_logits, graph, k_stop, stats, allowed)
+                               no_repeat_ngram_size, eos, return_logits, graph, k_stop, stats, allowed, samp)
     return outs, steps, carry

@@ -1013,3 +1013,48 @@ def gen_select_ids(scores: torch.Tensor, ids: torch.Tensor, seq: torch.Tensor, c
             raise RuntimeError("gen_select_ids: out must be a contiguous [nb] tensor")
     NV.call("kd_gen_select_ids", scores.data_ptr(), max(scores.stride(0), A), ids.data_ptr(), A, seq.data_ptr(),
             seq.shape[1], nb, cur.data_ptr(), float(repetition_penalty), int(no_repeat_ngram_size), _ptr(out), _stream())
+
+
+# ------------------------------------------------------------------------ sampling ----
+def gen_sample(scores: torch.Tensor, seq: torch.Tensor, cur: torch.Tensor, *, ids: torch.Tensor | None = None,
+               repetition_penalty: float = 1.0, no_repeat_ngram_size: int = 0, temperature: float = 1.0,
+               top_k: int = 0, top_p: float = 1.0, seed: int, streams: torch.Tensor,
+               out: torch.Tensor | None = None, u_out: torch.Tensor | None = None) -> torch.Tensor:
+    """gen_select_batch() / gen_select_ids() with the token drawn instead of the argmax
+    (kd_gen_sample): scores [nb, N] bf16 (N = V, or with ids [A] int32 ascending and unique N = A and
+    column j the score of token ids[j]), seq [nb, smax] int64, cur [nb] int32, streams [nb] int64 (the
+    rows' Philox stream ids), seed in [0, 2^64).  The processed scores of the select kernels, divided
+    by temperature, filtered by top_k (0: off) and top_p (1: off), then one draw with the row's
+    u(seed, streams[b], cur[b]); writes seq[b, cur[b]], out[b], cur[b] += 1 and u_out[b] (fp32, the u
+    used).  Row b depends on its own data and stream alone.  -> out."""
+    _require(scores, torch.bfloat16, "gen_sample.scores")
+    _require(seq, torch.int64, "gen_sample.seq")
+    _require(cur, torch.int32, "gen_sample.cur")
+    _require(streams, torch.int64, "gen_sample.streams")
+    if scores.dim() != 2 or scores.stride(1) != 1:
+        raise RuntimeError("gen_sample: scores must be [nb, N] with a contiguous last dim")
+    nb, N = scores.shape
+    if ids is not None and (_gather_ids(ids, "gen_sample") != N):
+        raise RuntimeError("gen_sample: scores must be [nb, A] for ids [A]")
+    if seq.dim() != 2 or seq.shape[0] != nb or not seq.is_contiguous() or cur.numel() != nb or not cur.is_contiguous():
+        raise RuntimeError("gen_sample: seq contiguous [nb, smax], cur contiguous [nb]")
+    if streams.numel() != nb or not streams.is_contiguous():
+        raise RuntimeError("gen_sample: streams must be a contiguous [nb] tensor")
+    if out is None:
+        out = torch.empty(nb, dtype=torch.int64, device=scores.device)
+    _require(out, torch.int64, "gen_sample.out")
+    if out.numel() != nb or not out.is_contiguous():
+        raise RuntimeError("gen_sample: out must be a contiguous [nb] tensor")
+    if u_out is not None:
+        _require(u_out, torch.float32, "gen_sample.u_out")
+        if u_out.numel() != nb or not u_out.is_contiguous():
+            raise RuntimeError("gen_sample: u_out must be a contiguous [nb] tensor")
+    seed = int(seed)
+    if not 0 <= seed < 1 << 64:
+        raise RuntimeError("gen_sample: seed must lie in [0, 2^64)")
+    nbytes = int(NV.lib().kd_gen_sample_workspace_size(nb, N))
+    ws = _workspace(("gen_sample", _stream()), nbytes, scores.device)
+    NV.call("kd_gen_sample", scores.data_ptr(), max(scores.stride(0), N), N, _ptr(ids), seq.data_ptr(), seq.shape[1], nb,
+            cur.data_ptr(), float(repetition_penalty), int(no_repeat_ngram_size), float(temperature), int(top_k),
+            float(top_p), seed, streams.data_ptr(), ws.data_ptr(), ws.numel(), out.data_ptr(), _ptr(u_out), _stream())
+    return out
