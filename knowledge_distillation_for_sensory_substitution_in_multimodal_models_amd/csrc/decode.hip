@@ -30,6 +30,9 @@
 //   gen_flags_row, gen_flags_ids, gen_processed
 //                    the processors' flag passes and the processed score of an entry: the selects
 //                    and k_gen_sample
+//   gen_ngram_scan, gen_block_argmax, gen_row / gen_row_store
+//                    the n-gram prefix match of both flag passes, the block argmax of both selects,
+//                    and the row frame (pointer, clamped length, stores) of the batched choosers
 //   gb_row_rstd, gb_stage_slab, gb_wave_order_sum, gb_store
 //                    the 16-row slab of k_gemv_batch and k_gemv_slabs, which is why a row of
 //                    kd_gemv_rows has kd_gemv_batch's bits; k_gemv_batch_reduce serves both
@@ -263,6 +266,19 @@ __global__ void __launch_bounds__(NT) k_gemv_wide(const bf16* __restrict__ x, co
     }
 }
 
+// NoRepeatNGramLogitsProcessor, the scan of both flag passes: the last (ngram - 1) tokens as a
+// prefix; ban(t) for the token t that followed every earlier occurrence of that prefix (only once
+// cur_len + 1 >= ngram).
+template <class Ban>
+__device__ __forceinline__ void gen_ngram_scan(const int64_t* __restrict__ seq, int len, int ngram, Ban ban) {
+    if (ngram > 0 && len + 1 >= ngram)
+        for (int i = threadIdx.x; i + ngram <= len; i += blockDim.x) {
+            bool match = true;
+            for (int k = 0; k < ngram - 1; ++k) match &= seq[i + k] == seq[len - ngram + 1 + k];
+            if (match) ban(seq[i + ngram - 1]);
+        }
+}
+
 // The token choice of one row by one workgroup of 1024 threads: V bytes of flags (bit 0 = seen,
 // bit 1 = banned) from the len ids of seq, then the processed-score argmax, which thread 0 returns
 // (the other threads' value is not the row's).  The vector paths need 16-byte aligned logits and
@@ -283,17 +299,9 @@ __device__ __forceinline__ void gen_flags_row(int V, const int64_t* __restrict__
             if (t >= 0 && t < V) flags[t] |= 1;
         }
     __syncthreads();   // the two processors OR different bits into the same bytes
-    // NoRepeatNGramLogitsProcessor: the last (ngram - 1) tokens as a prefix; ban the token that
-    // followed every earlier occurrence of that prefix (only once cur_len + 1 >= ngram)
-    if (ngram > 0 && len + 1 >= ngram)
-        for (int i = threadIdx.x; i + ngram <= len; i += blockDim.x) {
-            bool match = true;
-            for (int k = 0; k < ngram - 1; ++k) match &= seq[i + k] == seq[len - ngram + 1 + k];
-            if (match) {
-                const int64_t t = seq[i + ngram - 1];
-                if (t >= 0 && t < V) flags[t] |= 2;
-            }
-        }
+    gen_ngram_scan(seq, len, ngram, [&](int64_t t) {
+        if (t >= 0 && t < V) flags[t] |= 2;
+    });
     __syncthreads();
 }
 
@@ -305,10 +313,51 @@ __device__ __forceinline__ float gen_processed(float s, uint32_t f, float penalt
     return s;
 }
 
-__device__ __forceinline__ int gen_select_row(const bf16* __restrict__ logits, int V, const int64_t* __restrict__ seq,
-                                              int len, float penalty, int ngram, uint8_t* __restrict__ flags) {
+// The block argmax of the greedy kernels (1024 threads): every thread's (best, bi) in, the row's
+// winner out on thread 0 (the other threads' values are not the row's): the larger score, the lower
+// index on a tie, NaN never wins.  An index that no score ever set (0x7fffffff) becomes 0, what
+// torch.argmax returns for a row of -inf.
+__device__ __forceinline__ int gen_block_argmax(float& best, int bi) {
     __shared__ float sv[16];
     __shared__ int si[16];
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) {
+        const float ov = __shfl_xor(best, off, 64);
+        const int oi = __shfl_xor(bi, off, 64);
+        if (ov > best || (ov == best && oi < bi)) { best = ov; bi = oi; }
+    }
+    const int w = threadIdx.x >> 6;
+    if ((threadIdx.x & 63) == 0) { sv[w] = best; si[w] = bi; }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        for (int k = 1; k < (int)(blockDim.x >> 6); ++k)
+            if (sv[k] > best || (sv[k] == best && si[k] < bi)) { best = sv[k]; bi = si[k]; }
+        if (bi == 0x7fffffff) bi = 0;
+    }
+    return bi;
+}
+
+// The frame of the batched choosers (k_gen_select_batch, k_gen_select_ids, k_gen_sample), row
+// b = blockIdx.x: its sequence (row stride smax) and length cur_dev[b], kept inside the row so that
+// the ids read never leave it; gen_row_store (thread 0) writes the token.  A full row (len == smax)
+// still reports its token in out[b].
+struct GenRow {
+    int64_t* seq;
+    int len;
+};
+__device__ __forceinline__ GenRow gen_row(int64_t* __restrict__ seq_all, int smax, const int* __restrict__ cur_dev) {
+    const int b = blockIdx.x;
+    return {seq_all + (size_t)b * smax, max(0, min(cur_dev[b], smax))};
+}
+__device__ __forceinline__ void gen_row_store(const GenRow& r, int smax, int* __restrict__ cur_dev,
+                                              int64_t* __restrict__ out, int64_t tok) {
+    if (r.len < smax) r.seq[r.len] = tok;
+    if (out) out[blockIdx.x] = tok;
+    cur_dev[blockIdx.x] = r.len + 1;
+}
+
+__device__ __forceinline__ int gen_select_row(const bf16* __restrict__ logits, int V, const int64_t* __restrict__ seq,
+                                              int len, float penalty, int ngram, uint8_t* __restrict__ flags) {
     gen_flags_row(V, seq, len, penalty, ngram, flags);
     float best = -INFINITY;
     int bi = 0x7fffffff;
@@ -325,21 +374,7 @@ __device__ __forceinline__ int gen_select_row(const bf16* __restrict__ logits, i
         for (int e = 0; e < 8; ++e) consider(c * 8 + e, (float)lv[e], ((e < 4 ? fv.x : fv.y) >> (8 * (e & 3))) & 255u);
     }
     for (int i = (v8 << 3) + threadIdx.x; i < V; i += blockDim.x) consider(i, (float)logits[i], flags[i]);
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) {
-        const float ov = __shfl_xor(best, off, 64);
-        const int oi = __shfl_xor(bi, off, 64);
-        if (ov > best || (ov == best && oi < bi)) { best = ov; bi = oi; }
-    }
-    const int w = threadIdx.x >> 6;
-    if ((threadIdx.x & 63) == 0) { sv[w] = best; si[w] = bi; }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        for (int k = 1; k < (int)(blockDim.x >> 6); ++k)
-            if (sv[k] > best || (sv[k] == best && si[k] < bi)) { best = sv[k]; bi = si[k]; }
-        if (bi == 0x7fffffff) bi = 0;   // every score -inf: torch.argmax returns 0
-    }
-    return bi;
+    return gen_block_argmax(best, bi);
 }
 
 // seq [len + 1] int64 (the new token is written at seq[len]); len = *cur_dev, then incremented,
@@ -674,21 +709,17 @@ __global__ void __launch_bounds__(NT) k_gemv_batch_reduce(const float* __restric
     y[(size_t)b * N + n] = (bf16)v;
 }
 
-// k_gen_select for row b = blockIdx.x: its own logits row, sequence (row stride smax), length
-// cur_dev[b] and V bytes of flags.  A full row (len == smax) still reports its token in out[b].
+// k_gen_select for row b = blockIdx.x: its own logits row, sequence and length (gen_row) and V
+// bytes of flags.
 __global__ void __launch_bounds__(1024) k_gen_select_batch(const bf16* __restrict__ logits_all, int64_t ldl, int V,
                                                            int64_t* __restrict__ seq_all, int smax,
                                                            int* __restrict__ cur_dev, float penalty, int ngram,
                                                            uint8_t* __restrict__ flags_all, int64_t* __restrict__ out) {
     const int b = blockIdx.x;
-    int64_t* seq = seq_all + (size_t)b * smax;
-    const int len = max(0, min(cur_dev[b], smax));   // the ids read never leave the row
-    const int bi = gen_select_row(logits_all + (size_t)b * ldl, V, seq, len, penalty, ngram, flags_all + (size_t)b * V);
-    if (threadIdx.x == 0) {
-        if (len < smax) seq[len] = bi;
-        if (out) out[b] = bi;
-        cur_dev[b] = len + 1;
-    }
+    const GenRow r = gen_row(seq_all, smax, cur_dev);
+    const int bi = gen_select_row(logits_all + (size_t)b * ldl, V, r.seq, r.len, penalty, ngram,
+                                  flags_all + (size_t)b * V);
+    if (threadIdx.x == 0) gen_row_store(r, smax, cur_dev, out, bi);
 }
 
 // cos/sin row of position cur_dev[b] - 1 (kept inside the table) into row b of [nb, hh] buffers.
@@ -1057,7 +1088,7 @@ __device__ __forceinline__ int ids_find(const int* __restrict__ ids, int A, int6
 }
 
 // The flag pass of k_gen_select_ids over the A allowed entries (flags in LDS), shared with the
-// sampling kernel (k_gen_sample): ends on a barrier.
+// sampling kernel (k_gen_sample): ends on a barrier.  (Its three-line penalty loop stays its own.)
 __device__ __forceinline__ void gen_flags_ids(const int* __restrict__ ids, int A, const int64_t* __restrict__ seq,
                                               int len, float penalty, int ngram, uint8_t* flags) {
     for (int i = threadIdx.x; i < A; i += blockDim.x) flags[i] = 0;
@@ -1068,15 +1099,10 @@ __device__ __forceinline__ void gen_flags_ids(const int* __restrict__ ids, int A
             if (j >= 0) flags[j] = 1;
         }
     __syncthreads();   // the two processors set different bits of the same bytes
-    if (ngram > 0 && len + 1 >= ngram)
-        for (int i = threadIdx.x; i + ngram <= len; i += blockDim.x) {
-            bool match = true;
-            for (int k = 0; k < ngram - 1; ++k) match &= seq[i + k] == seq[len - ngram + 1 + k];
-            if (match) {
-                const int j = ids_find(ids, A, seq[i + ngram - 1]);
-                if (j >= 0) flags[j] |= 2;
-            }
-        }
+    gen_ngram_scan(seq, len, ngram, [&](int64_t t) {
+        const int j = ids_find(ids, A, t);
+        if (j >= 0) flags[j] |= 2;
+    });
     __syncthreads();
 }
 
@@ -1091,37 +1117,18 @@ __global__ void __launch_bounds__(1024) k_gen_select_ids(const bf16* __restrict_
                                                          int* __restrict__ cur_dev, float penalty, int ngram,
                                                          int64_t* __restrict__ out) {
     __shared__ uint8_t flags[KD_GEN_ALLOWED_MAX];
-    __shared__ float sv[16];
-    __shared__ int si[16];
-    const int b = blockIdx.x;
-    int64_t* seq = seq_all + (size_t)b * smax;
-    const bf16* scores = scores_all + (size_t)b * lds;
-    const int len = max(0, min(cur_dev[b], smax));   // the ids read never leave the row
-    gen_flags_ids(ids, A, seq, len, penalty, ngram, flags);
+    const GenRow r = gen_row(seq_all, smax, cur_dev);
+    const bf16* scores = scores_all + (size_t)blockIdx.x * lds;
+    gen_flags_ids(ids, A, r.seq, r.len, penalty, ngram, flags);
     float best = -INFINITY;
     int bj = 0x7fffffff;
     for (int j = threadIdx.x; j < A; j += blockDim.x) {
         const float s = gen_processed((float)scores[j], flags[j], penalty);
         if (s > best || (s == best && j < bj)) { best = s; bj = j; }   // NaN never wins
     }
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) {
-        const float ov = __shfl_xor(best, off, 64);
-        const int oj = __shfl_xor(bj, off, 64);
-        if (ov > best || (ov == best && oj < bj)) { best = ov; bj = oj; }
-    }
-    const int w = threadIdx.x >> 6;
-    if ((threadIdx.x & 63) == 0) { sv[w] = best; si[w] = bj; }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        for (int k = 1; k < (int)(blockDim.x >> 6); ++k)
-            if (sv[k] > best || (sv[k] == best && si[k] < bj)) { best = sv[k]; bj = si[k]; }
-        // best == -inf: every allowed entry is banned, -inf or NaN (bj is then entry 0 or none at all)
-        const int64_t tok = best == -INFINITY ? 0 : (int64_t)ids[bj];
-        if (len < smax) seq[len] = tok;
-        if (out) out[b] = tok;
-        cur_dev[b] = len + 1;
-    }
+    bj = gen_block_argmax(best, bj);
+    // best == -inf: every allowed entry is banned, -inf or NaN (bj is then some entry or none at all)
+    if (threadIdx.x == 0) gen_row_store(r, smax, cur_dev, out, best == -INFINITY ? 0 : (int64_t)ids[bj]);
 }
 
 // --------------------------------------------------------------- sampling (do_sample=True) ----
@@ -1314,11 +1321,11 @@ __global__ void __launch_bounds__(1024) k_gen_sample(const bf16* __restrict__ sc
     u64* tsum = (u64*)(row + lay.tsum_off);
     float* t = (float*)(row + lay.t_off);
     uint8_t* flags = IDS ? flags_s : row + lay.flags_off;
-    int64_t* seq = seq_all + (size_t)b * smax;
+    const GenRow r = gen_row(seq_all, smax, cur_dev);
+    const int len = r.len;
     const bf16* scores = scores_all + (size_t)b * lds;
-    const int len = max(0, min(cur_dev[b], smax));   // the ids read never leave the row
-    if constexpr (IDS) gen_flags_ids(ids, N, seq, len, penalty, ngram, flags);
-    else gen_flags_row(N, seq, len, penalty, ngram, flags);
+    if constexpr (IDS) gen_flags_ids(ids, N, r.seq, len, penalty, ngram, flags);
+    else gen_flags_row(N, r.seq, len, penalty, ngram, flags);
 
     // ---- pass 1
     const bool use_k = top_k >= 1 && top_k < N;
@@ -1486,9 +1493,7 @@ __global__ void __launch_bounds__(1024) k_gen_sample(const bf16* __restrict__ sc
         token = IDS ? (int64_t)ids[j] : (int64_t)j;
     }
     if (threadIdx.x == 0) {
-        if (len < smax) seq[len] = token;
-        out[b] = token;
-        cur_dev[b] = len + 1;
+        gen_row_store(r, smax, cur_dev, out, token);
         if (u_out) u_out[b] = (float)m24 * 5.9604644775390625e-08f;
     }
 }
@@ -1710,12 +1715,23 @@ int launch_attn_extend(const void* q, const void* k_new, const void* v_new, void
     return KD_OK;
 }
 
+// The checks the three batched choosers share: their pointers, a row of 1 <= N <= n_max scores (rule:
+// the entry's words for it) at stride ld in a sequence row of smax, 1 <= nb <= 16 rows, the processors.
+static int check_chooser_args(const char* who, bool pointers, int N, int n_max, const char* rule, int64_t ld, int smax,
+                              int nb, float penalty, int ngram) {
+    auto msg = [who](const std::string& what) { return std::string(who) + ": " + what; };
+    KD_CHECK_ARG(pointers, msg("null pointer"));
+    KD_CHECK_ARG(penalty > 0.f && ngram >= 0, msg("penalty must be > 0 and ngram >= 0"));
+    KD_CHECK_SHAPE(N >= 1 && N <= n_max && smax > 0 && ld >= N && nb >= 1 && nb <= GB_ROWS,
+                   msg(std::string(rule) + ", smax positive, ld >= its width, 1 <= nb <= 16"));
+    return KD_OK;
+}
+
 int launch_gen_select_batch(const void* logits, int64_t ldl, int V, int64_t* seq, int smax, int nb, int* cur_dev,
                             float penalty, int ngram, void* flags_ws, size_t ws_bytes, int64_t* out, void* stream) {
-    KD_CHECK_ARG(logits && seq && cur_dev && flags_ws, "gen_select_batch: null pointer");
-    KD_CHECK_SHAPE(V > 0 && smax > 0 && ldl >= V && nb >= 1 && nb <= GB_ROWS,
-                   "gen_select_batch: V, smax positive, ld >= V, 1 <= nb <= 16");
-    KD_CHECK_ARG(penalty > 0.f && ngram >= 0, "gen_select_batch: penalty must be > 0 and ngram >= 0");
+    if (int rc = check_chooser_args("gen_select_batch", logits && seq && cur_dev && flags_ws, V, INT_MAX, "V positive",
+                                    ldl, smax, nb, penalty, ngram))
+        return rc;
     if (ws_bytes < (size_t)nb * V) return fail(KD_ERR_WORKSPACE, "gen_select_batch: workspace must hold nb * V bytes");
     hipLaunchKernelGGL(k_gen_select_batch, dim3(nb), dim3(1024), 0, as_stream(stream), (const bf16*)logits, ldl, V, seq,
                        smax, cur_dev, penalty, ngram, (uint8_t*)flags_ws, out);
@@ -1858,10 +1874,9 @@ int launch_gemv_batch_gather(const void* x, int64_t ldx, int nb, const void* W, 
 
 int launch_gen_select_ids(const void* scores, int64_t lds, const int* ids, int A, int64_t* seq, int smax, int nb,
                           int* cur_dev, float penalty, int ngram, int64_t* out, void* stream) {
-    KD_CHECK_ARG(scores && ids && seq && cur_dev, "gen_select_ids: null pointer");
-    KD_CHECK_SHAPE(A >= 1 && A <= KD_GEN_ALLOWED_MAX && smax > 0 && lds >= A && nb >= 1 && nb <= GB_ROWS,
-                   "gen_select_ids: 1 <= A <= KD_GEN_ALLOWED_MAX, smax positive, ld >= A, 1 <= nb <= 16");
-    KD_CHECK_ARG(penalty > 0.f && ngram >= 0, "gen_select_ids: penalty must be > 0 and ngram >= 0");
+    if (int rc = check_chooser_args("gen_select_ids", scores && ids && seq && cur_dev, A, KD_GEN_ALLOWED_MAX,
+                                    "1 <= A <= KD_GEN_ALLOWED_MAX", lds, smax, nb, penalty, ngram))
+        return rc;
     hipLaunchKernelGGL(k_gen_select_ids, dim3(nb), dim3(1024), 0, as_stream(stream), (const bf16*)scores, lds, ids, A, seq,
                        smax, cur_dev, penalty, ngram, out);
     KD_LAUNCH_CHECK("k_gen_select_ids");
@@ -1878,14 +1893,13 @@ size_t gen_sample_ws(int nb, int N) {
 int launch_gen_sample(const void* scores, int64_t lds, int N, const int* ids, int64_t* seq, int smax, int nb,
                       int* cur_dev, float penalty, int ngram, float temperature, int top_k, float top_p, uint64_t seed,
                       const int64_t* streams, void* ws, size_t ws_bytes, int64_t* out, float* u_out, void* stream) {
-    KD_CHECK_ARG(scores && seq && cur_dev && streams && ws && out, "gen_sample: null pointer");
-    KD_CHECK_ARG(penalty > 0.f && ngram >= 0, "gen_sample: penalty must be > 0 and ngram >= 0");
+    if (int rc = check_chooser_args("gen_sample", scores && seq && cur_dev && streams && ws && out, N,
+                                    ids ? KD_GEN_ALLOWED_MAX : GS_N_MAX, "1 <= N <= 262144 (with ids: KD_GEN_ALLOWED_MAX)",
+                                    lds, smax, nb, penalty, ngram))
+        return rc;
     KD_CHECK_ARG(std::isfinite(temperature) && temperature > 0.f, "gen_sample: temperature must be finite and > 0");
     KD_CHECK_ARG(top_k >= 0, "gen_sample: top_k must be >= 0");
     KD_CHECK_ARG(top_p > 0.f && top_p <= 1.0f, "gen_sample: top_p must lie in (0, 1]");
-    KD_CHECK_SHAPE(N >= 1 && N <= (ids ? KD_GEN_ALLOWED_MAX : GS_N_MAX) && smax > 0 && lds >= N && nb >= 1 &&
-                       nb <= GB_ROWS,
-                   "gen_sample: 1 <= N <= 262144 (with ids: KD_GEN_ALLOWED_MAX), smax positive, ld >= N, 1 <= nb <= 16");
     KD_CHECK_SHAPE(ws_bytes >= gen_sample_ws(nb, N), "gen_sample: workspace smaller than kd_gen_sample_workspace_size");
     KD_CHECK_SHAPE(((uintptr_t)ws & 15) == 0, "gen_sample: workspace must be 16-byte aligned");
     if (ids)

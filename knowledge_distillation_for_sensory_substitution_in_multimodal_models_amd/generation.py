@@ -89,6 +89,10 @@ device work.  return_logits gives the raw rows, as in the greedy call.
 """
 from __future__ import annotations
 
+import copy
+import dataclasses
+import typing
+
 import torch
 
 from . import ops
@@ -98,7 +102,7 @@ from ._native import KD_GEMV_ROWS_MAX, KD_GEN_ALLOWED_MAX, KD_GEN_EOS_MAX
 EOS_TOKEN_IDS = (151645,)   # <|im_end|>: generation_config.eos_token_id of the -ov-hf chat checkpoints
 
 
-FUSE_NORM_DEFAULT = True   # RMSNorm fused into the decode GEMVs (tools/bench_generate.py passes fuse_norm for A/B)
+FUSE_NORM_DEFAULT = True   # RMSNorm fused into the decode GEMVs (generate(fuse_norm=False): the A/B route)
 
 
 # decode steps between two host reads of the rows still running (0: never stop early).  Measured
@@ -213,15 +217,6 @@ class _Allowed:
         """Full logits [nb, V] -> their allowed columns [nb, A], ascending ids."""
         return logits.index_select(1, self.cols)
 
-    def head(self, hn, w, batch: bool):
-        """The allowed logits [nb, A] of the final-norm rows hn."""
-        if self.gather:
-            return (ops.gemv_batch_gather if batch else ops.gemv_gather)(hn, w, self.ids)
-        return self.columns((ops.gemv_batch if batch else ops.gemv)(hn, w))
-
-    def select(self, scores, seq, cur, repetition_penalty, no_repeat_ngram_size, out=None):
-        ops.gen_select_ids(scores, self.ids, seq, cur, repetition_penalty, no_repeat_ngram_size, out=out)
-
 
 def _allowed(model, allowed_token_ids, restrict_head, who: str):
     if allowed_token_ids is None:
@@ -234,7 +229,7 @@ def _allowed(model, allowed_token_ids, restrict_head, who: str):
 class _Sampler:
     """The sampling settings of one call (do_sample=True), validated once, before any device work:
     temperature, top_k, top_p, the seed and one Philox stream id per prompt of the call.  rows(lo, hi)
-    is the part of a chunk: its stream ids on the device, fixed for the captured step."""
+    of the chooser puts a chunk's stream ids on the device, fixed for the captured step."""
 
     def __init__(self, temperature, top_k, top_p, seed, sample_streams, n_rows: int, who: str):
         import math
@@ -265,37 +260,92 @@ class _Sampler:
         self.temperature, self.top_k, self.top_p = float(t), min(int(top_k), 2 ** 31 - 1), float(top_p)
         self.seed, self.streams = int(seed), [int(v) for v in streams]
 
-    def rows(self, dev, lo: int, hi: int):
-        return _SamplerRows(self, torch.tensor(self.streams[lo:hi], dtype=torch.int64, device=dev))
+
+class _Chooser:
+    """The token choice of one call: the one place that knows whether a token is drawn (sampler), taken among the
+    allowed ids (allowed) or the plain argmax, and which head the scores come from.  rows(): one chunk's chooser."""
+
+    def __init__(self, model, repetition_penalty, no_repeat_ngram_size, allowed, sampler):
+        self.model, self.allowed, self.sampler, self.single, self.streams = model, allowed, sampler, False, None
+        self.processors = (repetition_penalty, no_repeat_ngram_size)
+
+    def rows(self, lo: int, hi: int, single: bool = False):
+        """Prompts [lo, hi) of the call: their stream ids on the device.  single: generate(), plain kd_gen_select."""
+        c = copy.copy(self)
+        c.single = single
+        if self.sampler is not None:
+            c.streams = torch.tensor(self.sampler.streams[lo:hi], dtype=torch.int64, device=self.model.device)
+        return c
+
+    def head(self, hn, batch: bool):
+        """Final-norm rows hn -> logits [nb, V], or [nb, A] of the allowed ids (gathered head or the full head's)."""
+        w, a = self.model.lm_head_weight(), self.allowed
+        if a is not None and a.gather:
+            return ops.gemv_batch_gather(hn, w, a.ids) if batch else ops.gemv_gather(hn, w, a.ids)
+        lg = (ops.gemv_batch if batch else ops.gemv)(hn, w)
+        return lg if a is None else a.columns(lg)
+
+    def choose(self, scores, seq, cur, out=None, row=None):
+        """Every row's next token from head()'s scores: seq[b, cur[b]], out[b], cur[b] += 1.  row = b: row b alone."""
+        a, s = self.allowed, self.sampler
+        if s is not None:   # kd_gen_sample in place of the select of the same scores
+            ops.gen_sample(scores, seq, cur, ids=None if a is None else a.ids, repetition_penalty=self.processors[0],
+                           no_repeat_ngram_size=self.processors[1], temperature=s.temperature, top_k=s.top_k,
+                           top_p=s.top_p, seed=s.seed, out=out,
+                           streams=self.streams if row is None else self.streams[row:row + 1])
+        elif a is not None:
+            ops.gen_select_ids(scores, a.ids, seq, cur, *self.processors, out=out)
+        elif self.single:
+            ops.gen_select(scores, seq, 0, *self.processors, out=out, cur=cur)
+        else:
+            ops.gen_select_batch(scores, seq, cur, *self.processors, out=out)
+
+    def first(self, logits, seq_row, L: int, row: int):
+        """The prefill's token from the prompt's full logits row [1, V], into seq_row [1, smax] at L -> the row kept."""
+        if self.allowed is not None:
+            logits = self.allowed.columns(logits)
+        if self.allowed is None and self.sampler is None:
+            ops.gen_select(logits, seq_row, L, *self.processors)
+        else:
+            self.choose(logits, seq_row, torch.full((1,), L, dtype=torch.int32, device=logits.device), row=row)
+        return logits
 
 
-class _SamplerRows:
-    def __init__(self, s: _Sampler, streams):
-        self.s, self.streams = s, streams
+@dataclasses.dataclass
+class _Run:
+    """The decode settings of one call, as its entry point checked them; rows() is a chunk's."""
+    max_new_tokens: int
+    eos: set
+    return_logits: bool
+    graph: bool
+    k_stop: int
+    stats: dict | None
+    chooser: _Chooser
 
-    def draw(self, allowed, scores, seq, cur, repetition_penalty, no_repeat_ngram_size, out=None, row=None):
-        """kd_gen_sample in place of the select of the same scores: over all rows of the chunk, or
-        (row = b: scores [1, N], seq [1, smax], cur [1]) with row b's stream."""
-        s = self.s
-        streams = self.streams if row is None else self.streams[row:row + 1]
-        ops.gen_sample(scores, seq, cur, ids=None if allowed is None else allowed.ids,
-                       repetition_penalty=repetition_penalty, no_repeat_ngram_size=no_repeat_ngram_size,
-                       temperature=s.temperature, top_k=s.top_k, top_p=s.top_p, seed=s.seed, streams=streams, out=out)
-
-
-def _sampler(do_sample, temperature, top_k, top_p, seed, sample_streams, n_rows: int, stats, who: str):
-    """None for the greedy call (temperature, top_k, top_p, seed and sample_streams are then ignored,
-    as transformers ignores its warpers when not sampling)."""
-    if not do_sample:
-        return None
-    s = _Sampler(temperature, top_k, top_p, seed, sample_streams, n_rows, who)
-    if stats is not None:
-        stats["seed"] = s.seed
-    return s
+    def rows(self, lo: int, hi: int) -> "_Run":
+        return dataclasses.replace(self, chooser=self.chooser.rows(lo, hi))
 
 
-def _decode_layers(model):
-    """Per layer: (input norm, q|k|v weight, q|k|v bias, o_proj, post-attention norm, gate|up, down)."""
+def _begin(who: str, model, n_rows: int, stop_check_every, allowed_token_ids, restrict_head, stats, sampling):
+    """The entry points' front matter, every ValueError before any device work: stop_check_every, allowed_token_ids /
+    restrict_head, the stats keys, then sampling = (do_sample, temperature, top_k, top_p, seed, sample_streams) for
+    n_rows prompts (do_sample=False: ignored, as transformers ignores its warpers) -> (k_stop, _Allowed, _Sampler)."""
+    k_stop = _stop_every(stop_check_every, who)
+    allowed = _allowed(model, allowed_token_ids, restrict_head, who)
+    _stats_begin(stats)
+    sampler = _Sampler(*sampling[1:], n_rows, who) if sampling[0] else None
+    if sampler is not None and stats is not None:
+        stats["seed"] = sampler.seed
+    return k_stop, allowed, sampler
+
+
+class _Layers(typing.NamedTuple):
+    eps: float
+    inter: int
+    weights: list   # per layer: (input norm, q|k|v weight, q|k|v bias, o_proj, post-attention norm, gate|up, down)
+
+
+def _decode_layers(model) -> _Layers:
     T, P = model.cfg.text, model.P
     qd, kd = T.heads * T.head_dim, T.kv_heads * T.head_dim
     lp = "language_model.model."
@@ -308,7 +358,52 @@ def _decode_layers(model):
                        P[p + "self_attn.o_proj.weight"], P[p + "post_attention_layernorm.weight"],
                        P.span(p + "mlp.gate_proj.weight", p + "mlp.up_proj.weight", 2 * T.inter, T.hidden),
                        P[p + "mlp.down_proj.weight"]))
-    return layers
+    return _Layers(T.eps, T.inter, layers)
+
+
+def _layer_pass(x, layers: _Layers, linear, attend):
+    """x through every decoder layer; linear: ops.gemv / gemv_batch / gemv_rows; attend(i, qkv): layer i's attention."""
+    for i, (w_in, Wqkv, bqkv, Wo, w_post, Wgu, Wdown) in enumerate(layers.weights):
+        qkv = linear(x, Wqkv, bias=bqkv, norm_w=w_in, eps=layers.eps)      # input_layernorm fused
+        o = attend(i, qkv)
+        x_mid = linear(o, Wo, residual=x)
+        a = linear(x_mid, Wgu, swiglu_inter=layers.inter, norm_w=w_post, eps=layers.eps)  # post_attention_layernorm
+        x = linear(a, Wdown, residual=x_mid)
+    return x
+
+
+def _gemv_unfused(x, w, norm_w=None, eps=None, **epilogue):
+    """ops.gemv with the RMSNorm as its own launch in front (generate()'s fuse_norm=False A/B route)."""
+    if norm_w is not None:
+        x, _, _ = ops.norm_fwd(x, norm_w, None, eps, rms=True, save_stats=False)
+    return ops.gemv(x, w, **epilogue)
+
+
+def _final_norm(model, x):
+    # its own launch: fused into the 38k-workgroup lm_head GEMV every workgroup would recompute it (measured slower)
+    return ops.norm_fwd(x, model.P["language_model.model.norm.weight"], None, model.cfg.text.eps, rms=True,
+                        save_stats=False)[0]
+
+
+def _prefill(model, prompt, kc, vc, seq_row, chooser: _Chooser, row: int = 0):
+    """One prompt (input_ids, pixel_values, image_sizes) of generate() / generate_batch(): the training forward, its
+    roped k/v kept in the cache views kc, vc [layers, HKV, smax, hd], the ids in seq_row [1, smax] and the first token
+    behind them (row: the prompt's slot in its chunk) -> (its logits row, the last layer's k/v).  The caller holds both
+    while it decodes: freed, their storage is in the allocator's cache, which torch.cuda.graph empties before a capture
+    and the next forward refills (1.7 ms per generate() call, profiles/generate_chooser/bench_ab.txt)."""
+    input_ids, pixel_values, image_sizes = prompt
+    L = int(input_ids.shape[1])
+    kv = []
+    fwd = model.forward(input_ids, pixel_values, image_sizes, save=False, kv_out=kv)
+    for i, (k, v) in enumerate(kv):
+        kc[i, :, :L].copy_(k[0])
+        vc[i, :, :L].copy_(v[0])
+    held = kv[-1]
+    del kv
+    seq_row[0, :L].copy_(input_ids[0])
+    logits = model.logits(fwd["hn"][L - 1:L])
+    del fwd
+    return chooser.first(logits, seq_row, L, row), held
 
 
 def _run_steps(step, n_steps: int, graph: bool, stop: _Stop, on_logits=None) -> int:
@@ -373,104 +468,60 @@ def generate(model, input_ids: torch.Tensor, pixel_values: torch.Tensor, image_s
     allowed_token_ids, restrict_head: constrained decoding, see the module docstring (the logits
     returned are then the compact rows [1, A])."""
     del pad_token_id   # batch of one: no padding of finished rows
-    k_stop = _stop_every(stop_check_every, "generate")
-    allowed = _allowed(model, allowed_token_ids, restrict_head, "generate")
-    _stats_begin(stats)
-    sampler = _sampler(do_sample, temperature, top_k, top_p, seed, sample_streams, 1, stats, "generate")
-    FUSE_NORM = FUSE_NORM_DEFAULT if fuse_norm is None else bool(fuse_norm)
+    k_stop, allowed, sampler = _begin("generate", model, 1, stop_check_every, allowed_token_ids, restrict_head, stats,
+                                      (do_sample, temperature, top_k, top_p, seed, sample_streams))
     if input_ids.dim() != 2 or input_ids.shape[0] != 1:
         raise ValueError("generate: batch size 1 (as evaluate_onevision.py runs it)")
-    T, P = model.cfg.text, model.P
+    chooser = _Chooser(model, repetition_penalty, no_repeat_ngram_size, allowed, sampler).rows(0, 1, single=True)
+    T = model.cfg.text
     dev = model.device
     L = int(input_ids.shape[1])
     smax = L + int(max_new_tokens)
     eos = _eos_set(eos_token_id)
     nq, nkv, hd = T.heads, T.kv_heads, T.head_dim
-    lp = "language_model.model."
 
     # ---- prefill: the training forward, its roped k/v kept
-    kv = []
-    fwd = model.forward(input_ids, pixel_values, image_sizes, save=False, kv_out=kv)
     kc = torch.empty((T.layers, nkv, smax, hd), dtype=torch.bfloat16, device=dev)
     vc = torch.empty_like(kc)
-    for i, (k, v) in enumerate(kv):
-        kc[i, :, :L].copy_(k[0])
-        vc[i, :, :L].copy_(v[0])
-    del kv
-    seq = torch.empty(smax, dtype=torch.int64, device=dev)
-    seq[:L].copy_(input_ids[0])
-    logits = model.logits(fwd["hn"][L - 1:L])
-    del fwd
-    samp = None if sampler is None else sampler.rows(dev, 0, 1)
-    if allowed is not None:
-        logits = allowed.columns(logits)
-    if samp is not None:
-        samp.draw(allowed, logits, seq.view(1, smax), torch.full((1,), L, dtype=torch.int32, device=dev),
-                  repetition_penalty, no_repeat_ngram_size)
-    elif allowed is None:
-        ops.gen_select(logits, seq, L, repetition_penalty, no_repeat_ngram_size)
-    else:
-        allowed.select(logits, seq.view(1, smax), torch.full((1,), L, dtype=torch.int32, device=dev),
-                       repetition_penalty, no_repeat_ngram_size)
-    steps = [logits] if return_logits else None
+    seq = torch.empty((1, smax), dtype=torch.int64, device=dev)
+    first, held = _prefill(model, (input_ids, pixel_values, image_sizes), kc, vc, seq, chooser)
+    steps = [first]
 
     cos, sin = model._rope_for(smax)
     src = torch.full((1,), -2, dtype=torch.int32, device=dev)   # token embedding (kd_embed_assemble)
-    table = P[lp + "embed_tokens.weight"]
+    table = model.P["language_model.model.embed_tokens.weight"]
     layers = _decode_layers(model)
+    linear = ops.gemv if (FUSE_NORM_DEFAULT if fuse_norm is None else bool(fuse_norm)) else _gemv_unfused
     # device-resident step state: the sequence length (tokens so far, the one being decoded
     # included), the token being decoded and its RoPE row -> every launch of a step has fixed
     # arguments and the step replays from one captured HIP graph
     cur = torch.full((1,), L + 1, dtype=torch.int32, device=dev)
-    tok = seq[L:L + 1].clone()   # the token being decoded (kd_gen_select rewrites it each step)
+    tok = seq[0, L:L + 1].clone()   # the token being decoded (the chooser rewrites it each step)
     cos_row = torch.empty((1, cos.shape[1]), dtype=torch.float32, device=dev)
     sin_row = torch.empty_like(cos_row)
     stop = _Stop(model, 1, eos, k_stop)
     stop.mark(tok, cur)   # the prefill's token
 
+    def attend(i, qkv):
+        q, k, v = ops.qkv_split(qkv, 1, 1, nq, nkv, hd, hd, cos_row, sin_row)
+        return ops.attn_decode(q.view(nq, hd), k.view(nkv, hd), v.view(nkv, hd), kc[i], vc[i], 0, hd, cur=cur)
+
     def step():
         ops.rope_row(cos, sin, cur, cos_row, sin_row)
-        x = ops.embed_assemble(tok, src, table, None, None, model.err)
-        for i, (w_in, Wqkv, bqkv, Wo, w_post, Wgu, Wdown) in enumerate(layers):
-            if FUSE_NORM:
-                qkv = ops.gemv(x, Wqkv, bias=bqkv, norm_w=w_in, eps=T.eps)      # input_layernorm fused
-            else:
-                h, _, _ = ops.norm_fwd(x, w_in, None, T.eps, rms=True, save_stats=False)
-                qkv = ops.gemv(h, Wqkv, bias=bqkv)
-            q, k, v = ops.qkv_split(qkv, 1, 1, nq, nkv, hd, hd, cos_row, sin_row)
-            o = ops.attn_decode(q.view(nq, hd), k.view(nkv, hd), v.view(nkv, hd), kc[i], vc[i], 0, hd, cur=cur)
-            x_mid = ops.gemv(o, Wo, residual=x)
-            if FUSE_NORM:
-                a = ops.gemv(x_mid, Wgu, swiglu_inter=T.inter, norm_w=w_post, eps=T.eps)  # post_attention_layernorm
-            else:
-                h2, _, _ = ops.norm_fwd(x_mid, w_post, None, T.eps, rms=True, save_stats=False)
-                a = ops.gemv(h2, Wgu, swiglu_inter=T.inter)
-            x = ops.gemv(a, Wdown, residual=x_mid)
-        # final norm as its own launch: fused into the 38k-workgroup lm_head GEMV it would be recomputed
-        # by every workgroup (measured slower)
-        hn, _, _ = ops.norm_fwd(x, P[lp + "norm.weight"], None, T.eps, rms=True, save_stats=False)
-        if allowed is None:
-            lg = ops.gemv(hn, model.lm_head_weight())
-        else:
-            lg = allowed.head(hn, model.lm_head_weight(), batch=False)
-        if samp is not None:
-            samp.draw(allowed, lg, seq.view(1, smax), cur, repetition_penalty, no_repeat_ngram_size, out=tok)
-        elif allowed is None:
-            ops.gen_select(lg, seq, 0, repetition_penalty, no_repeat_ngram_size, out=tok, cur=cur)
-        else:
-            allowed.select(lg, seq.view(1, smax), cur, repetition_penalty, no_repeat_ngram_size, out=tok)
+        x = _layer_pass(ops.embed_assemble(tok, src, table, None, None, model.err), layers, linear, attend)
+        lg = chooser.head(_final_norm(model, x), batch=False)
+        chooser.choose(lg, seq, cur, out=tok)
         stop.mark(tok, cur)
         return lg
 
     n_steps = smax - (L + 1)
     ran = _run_steps(step, n_steps, graph, stop, (lambda lg: steps.append(lg.clone())) if return_logits else None)
-    end = _first_eos(stop, seq.view(1, smax), [L], int(max_new_tokens), eos)[0]
+    del held   # not before the decode is over: see _prefill
+    end = _first_eos(stop, seq, [L], int(max_new_tokens), eos)[0]
     n = end or smax
-    if return_logits:
-        steps = steps[:n - L]
     _stats_chunk(stats, ran, n_steps, stop.checks, [end])
-    out = seq[:n].view(1, n)
-    return (out, steps) if return_logits else out
+    out = seq[0, :n].view(1, n)
+    return (out, steps[:n - L]) if return_logits else out
 
 
 MAX_BATCH = 16   # rows per decode step: the M dimension of the MFMA behind kd_gemv_batch
@@ -503,12 +554,10 @@ def generate_batch(model, prompts, max_new_tokens: int = 32, repetition_penalty:
     top_p, seed, sample_streams (one stream id per prompt; default: its index): module docstring,
     "Sampling"; a row's tokens depend on its prompt, the settings, seed and its own stream only."""
     del pad_token_id   # finished rows are cut, not padded
-    k_stop = _stop_every(stop_check_every, "generate_batch")
-    allowed = _allowed(model, allowed_token_ids, restrict_head, "generate_batch")
-    _stats_begin(stats)
     prompts = list(prompts)
-    sampler = _sampler(do_sample, temperature, top_k, top_p, seed, sample_streams, len(prompts), stats,
-                       "generate_batch")
+    sampling = (do_sample, temperature, top_k, top_p, seed, sample_streams)
+    k_stop, allowed, sampler = _begin("generate_batch", model, len(prompts), stop_check_every, allowed_token_ids,
+                                      restrict_head, stats, sampling)
     if not prompts:
         raise ValueError("generate_batch: no prompts")
     if int(max_new_tokens) < 1:
@@ -516,102 +565,64 @@ def generate_batch(model, prompts, max_new_tokens: int = 32, repetition_penalty:
     for ids, _, _ in prompts:
         if ids.dim() != 2 or ids.shape[0] != 1:
             raise ValueError("generate_batch: every prompt's input_ids must be [1, L]")
+    run = _Run(int(max_new_tokens), _eos_set(eos_token_id), return_logits, graph, k_stop, stats,
+               _Chooser(model, repetition_penalty, no_repeat_ngram_size, allowed, sampler))
     outs, logs = [], []
     for c0 in range(0, len(prompts), MAX_BATCH):
-        o, lg = _generate_rows(model, prompts[c0:c0 + MAX_BATCH], int(max_new_tokens), repetition_penalty,
-                               no_repeat_ngram_size, eos_token_id, return_logits, graph, k_stop, stats, allowed,
-                               None if sampler is None else sampler.rows(model.device, c0, c0 + MAX_BATCH))
+        o, lg = _generate_rows(model, prompts[c0:c0 + MAX_BATCH], run.rows(c0, c0 + MAX_BATCH))
         outs += o
         logs += lg
     return (outs, logs) if return_logits else outs
 
 
-def _generate_rows(model, prompts, max_new_tokens, repetition_penalty, no_repeat_ngram_size, eos_token_id,
-                   return_logits, graph, k_stop, stats, allowed, samp=None):
+def _generate_rows(model, prompts, run: _Run):
     T = model.cfg.text
-    dev = model.device
     nb = len(prompts)
     Ls = [int(ids.shape[1]) for ids, _, _ in prompts]
-    smax = max(Ls) + max_new_tokens
-    eos = _eos_set(eos_token_id)
-    nkv, hd = T.kv_heads, T.head_dim
+    smax = max(Ls) + run.max_new_tokens
 
     # ---- prefill, one prompt at a time: generate()'s own (row b of the caches and of seq)
-    kc = torch.empty((T.layers, nb, nkv, smax, hd), dtype=torch.bfloat16, device=dev)
+    kc = torch.empty((T.layers, nb, T.kv_heads, smax, T.head_dim), dtype=torch.bfloat16, device=model.device)
     vc = torch.empty_like(kc)
-    seq = torch.zeros((nb, smax), dtype=torch.int64, device=dev)
+    seq = torch.zeros((nb, smax), dtype=torch.int64, device=model.device)
     steps = [[] for _ in range(nb)]
-    for b, (input_ids, pixel_values, image_sizes) in enumerate(prompts):
-        L = Ls[b]
-        kv = []
-        fwd = model.forward(input_ids, pixel_values, image_sizes, save=False, kv_out=kv)
-        for i, (k, v) in enumerate(kv):
-            kc[i, b, :, :L].copy_(k[0])
-            vc[i, b, :, :L].copy_(v[0])
-        del kv
-        seq[b, :L].copy_(input_ids[0])
-        logits = model.logits(fwd["hn"][L - 1:L])
-        del fwd
-        if allowed is not None:
-            logits = allowed.columns(logits)
-        if samp is not None:
-            samp.draw(allowed, logits, seq[b:b + 1], torch.full((1,), L, dtype=torch.int32, device=dev),
-                      repetition_penalty, no_repeat_ngram_size, row=b)
-        elif allowed is None:
-            ops.gen_select(logits, seq[b], L, repetition_penalty, no_repeat_ngram_size)
-        else:
-            allowed.select(logits, seq[b:b + 1], torch.full((1,), L, dtype=torch.int32, device=dev),
-                           repetition_penalty, no_repeat_ngram_size)
-        if return_logits:
-            steps[b].append(logits)
-
-    return _decode_rows(model, kc, vc, seq, Ls, steps, max_new_tokens, repetition_penalty, no_repeat_ngram_size, eos,
-                        return_logits, graph, k_stop, stats, allowed, samp)
+    for b, prompt in enumerate(prompts):
+        first, held = _prefill(model, prompt, kc[:, b], vc[:, b], seq[b:b + 1], run.chooser, b)
+        steps[b].append(first)
+    done = _decode_rows(model, kc, vc, seq, Ls, steps, run)
+    del held   # not before the decode is over: see _prefill
+    return done
 
 
-def _decode_rows(model, kc, vc, seq, Ls, steps, max_new_tokens, repetition_penalty, no_repeat_ngram_size, eos,
-                 return_logits, graph, k_stop, stats, allowed=None, samp=None):
+def _decode_rows(model, kc, vc, seq, Ls, steps, run: _Run):
     """The batched decode loop behind generate_batch() and generate_grouped(): row b's caches hold
     its L_b prompt positions, seq[b, L_b] its first new token and steps[b] that token's logits row.
     The loop ends early once every row has emitted an EOS (_Stop)."""
-    T, P = model.cfg.text, model.P
+    T = model.cfg.text
     dev = model.device
     nb, smax = seq.shape
     nq, nkv, hd = T.heads, T.kv_heads, T.head_dim
-    lp = "language_model.model."
     cos, sin = model._rope_for(smax)
     src = torch.full((nb,), -2, dtype=torch.int32, device=dev)   # token embedding (kd_embed_assemble)
-    table = P[lp + "embed_tokens.weight"]
+    table = model.P["language_model.model.embed_tokens.weight"]
     layers = _decode_layers(model)
     # device-resident per-row step state (generate()'s, one entry per row)
     cur = torch.tensor([L + 1 for L in Ls], dtype=torch.int32, device=dev)
     tok = torch.stack([seq[b, Ls[b]] for b in range(nb)])   # the tokens being decoded
     cos_rows = torch.empty((nb, cos.shape[1]), dtype=torch.float32, device=dev)
     sin_rows = torch.empty_like(cos_rows)
-    stop = _Stop(model, nb, eos, k_stop)
+    stop = _Stop(model, nb, run.eos, run.k_stop)
     stop.mark(tok, cur)   # the prefill's tokens
+
+    def attend(i, qkv):
+        q, k, v = ops.qkv_split(qkv, 1, nb, nq, nkv, hd, hd, cos_rows, sin_rows)   # token b rotated by row b
+        return ops.attn_decode_batch(q[0], k[0], v[0], kc[i], vc[i], cur, hd)
 
     def step():
         ops.rope_rows(cos, sin, cur, cos_rows, sin_rows)
-        x = ops.embed_assemble(tok, src, table, None, None, model.err)
-        for i, (w_in, Wqkv, bqkv, Wo, w_post, Wgu, Wdown) in enumerate(layers):
-            qkv = ops.gemv_batch(x, Wqkv, bias=bqkv, norm_w=w_in, eps=T.eps)      # input_layernorm fused
-            q, k, v = ops.qkv_split(qkv, 1, nb, nq, nkv, hd, hd, cos_rows, sin_rows)   # token b rotated by row b
-            o = ops.attn_decode_batch(q[0], k[0], v[0], kc[i], vc[i], cur, hd)
-            x_mid = ops.gemv_batch(o, Wo, residual=x)
-            a = ops.gemv_batch(x_mid, Wgu, swiglu_inter=T.inter, norm_w=w_post, eps=T.eps)  # post_attention_layernorm
-            x = ops.gemv_batch(a, Wdown, residual=x_mid)
-        hn, _, _ = ops.norm_fwd(x, P[lp + "norm.weight"], None, T.eps, rms=True, save_stats=False)
-        if allowed is None:
-            lg = ops.gemv_batch(hn, model.lm_head_weight())
-        else:
-            lg = allowed.head(hn, model.lm_head_weight(), batch=True)
-        if samp is not None:
-            samp.draw(allowed, lg, seq, cur, repetition_penalty, no_repeat_ngram_size, out=tok)
-        elif allowed is None:
-            ops.gen_select_batch(lg, seq, cur, repetition_penalty, no_repeat_ngram_size, out=tok)
-        else:
-            allowed.select(lg, seq, cur, repetition_penalty, no_repeat_ngram_size, out=tok)
+        x = _layer_pass(ops.embed_assemble(tok, src, table, None, None, model.err), layers, ops.gemv_batch, attend)
+        lg = run.chooser.head(_final_norm(model, x), batch=True)
+        run.chooser.choose(lg, seq, cur, out=tok)
         stop.mark(tok, cur)
         return lg
 
@@ -620,16 +631,14 @@ def _decode_rows(model, kc, vc, seq, Ls, steps, max_new_tokens, repetition_penal
         for b in range(nb):
             steps[b].append(lg[b:b + 1])
 
-    n_steps = max_new_tokens - 1
-    ran = _run_steps(step, n_steps, graph, stop, keep if return_logits else None)
+    n_steps = run.max_new_tokens - 1
+    ran = _run_steps(step, n_steps, run.graph, stop, keep if run.return_logits else None)
     # every row is cut after its own first EOS (fin[b]: its length there, 0 if none)
-    fin = _first_eos(stop, seq, Ls, max_new_tokens, eos)
-    ends = [fin[b] or L + max_new_tokens for b, L in enumerate(Ls)]
-    for b, L in enumerate(Ls):
-        steps[b] = steps[b][:ends[b] - L]
-    _stats_chunk(stats, ran, n_steps, stop.checks, fin)
+    fin = _first_eos(stop, seq, Ls, run.max_new_tokens, run.eos)
+    ends = [fin[b] or L + run.max_new_tokens for b, L in enumerate(Ls)]
+    _stats_chunk(run.stats, ran, n_steps, stop.checks, fin)
     outs = [seq[b, :ends[b]].view(1, ends[b]) for b in range(nb)]
-    return outs, (steps if return_logits else [])
+    return outs, ([steps[b][:ends[b] - L] for b, L in enumerate(Ls)] if run.return_logits else [])
 
 
 @torch.no_grad()
@@ -665,12 +674,10 @@ def generate_grouped(model, groups, max_new_tokens: int = 32, repetition_penalty
     stream id per question in the flattened order of the groups (default: that index), and the token
     behind the extend pass is drawn too."""
     del pad_token_id   # finished rows are cut, not padded
-    k_stop = _stop_every(stop_check_every, "generate_grouped")
-    allowed = _allowed(model, allowed_token_ids, restrict_head, "generate_grouped")
-    _stats_begin(stats)
     groups = [(px, sizes, list(qs)) for px, sizes, qs in groups]
-    sampler = _sampler(do_sample, temperature, top_k, top_p, seed, sample_streams, sum(len(qs) for _, _, qs in groups),
-                       stats, "generate_grouped")
+    sampling = (do_sample, temperature, top_k, top_p, seed, sample_streams)
+    k_stop, allowed, sampler = _begin("generate_grouped", model, sum(len(qs) for _, _, qs in groups), stop_check_every,
+                                      allowed_token_ids, restrict_head, stats, sampling)
     if not groups:
         raise ValueError("generate_grouped: no groups")
     if int(max_new_tokens) < 1:
@@ -697,31 +704,27 @@ def generate_grouped(model, groups, max_new_tokens: int = 32, repetition_penalty
             if len(host) - P0 > KD_GEMV_ROWS_MAX:
                 raise ValueError(f"generate_grouped: more than {KD_GEMV_ROWS_MAX} tokens after the image")
             items.append((gi, px, sizes, ids, P0))
+    run = _Run(int(max_new_tokens), _eos_set(eos_token_id), return_logits, graph, k_stop, stats,
+               _Chooser(model, repetition_penalty, no_repeat_ngram_size, allowed, sampler))
     outs, logs = [[] for _ in groups], [[] for _ in groups]
     carry = (None, None)   # the prefix K/V of the group a chunk ended in: its next chunk reuses them
     for c0 in range(0, len(items), MAX_BATCH):
         chunk = items[c0:c0 + MAX_BATCH]
-        o, lg, carry = _generate_grouped_rows(model, chunk, carry, int(max_new_tokens), repetition_penalty,
-                                              no_repeat_ngram_size, eos_token_id, return_logits, graph, k_stop,
-                                              stats, allowed,
-                                              None if sampler is None else sampler.rows(model.device, c0, c0 + MAX_BATCH))
+        o, lg, carry = _generate_grouped_rows(model, chunk, carry, run.rows(c0, c0 + MAX_BATCH))
         for (gi, *_), ob, lb in zip(chunk, o, lg if return_logits else [None] * len(o)):
             outs[gi].append(ob)
             logs[gi].append(lb)
     return (outs, logs) if return_logits else outs
 
 
-def _generate_grouped_rows(model, chunk, carry, max_new_tokens, repetition_penalty, no_repeat_ngram_size, eos_token_id,
-                           return_logits, graph, k_stop, stats, allowed, samp=None):
-    T, P = model.cfg.text, model.P
+def _generate_grouped_rows(model, chunk, carry, run: _Run):
+    T = model.cfg.text
     dev = model.device
     nb = len(chunk)
     Ls = [int(ids.shape[1]) for _, _, _, ids, _ in chunk]
     P0s = [P0 for *_, P0 in chunk]
-    smax = max(Ls) + max_new_tokens
-    eos = _eos_set(eos_token_id)
+    smax = max(Ls) + run.max_new_tokens
     nq, nkv, hd = T.heads, T.kv_heads, T.head_dim
-    lp = "language_model.model."
 
     kc = torch.empty((T.layers, nb, nkv, smax, hd), dtype=torch.bfloat16, device=dev)
     vc = torch.empty_like(kc)
@@ -740,7 +743,7 @@ def _generate_grouped_rows(model, chunk, carry, max_new_tokens, repetition_penal
     # ---- extend pass: every suffix row of the chunk through the layers at once (sub-ranges of
     # questions only if the rows exceed the kernels' cap; a question's bits do not depend on the split)
     cos, sin = model._rope_for(smax)
-    table = P[lp + "embed_tokens.weight"]
+    table = model.P["language_model.model.embed_tokens.weight"]
     layers = _decode_layers(model)
     last = []
     b0 = 0
@@ -761,30 +764,19 @@ def _generate_grouped_rows(model, chunk, carry, max_new_tokens, repetition_penal
         cos_rows = torch.empty((R, cos.shape[1]), dtype=torch.float32, device=dev)
         sin_rows = torch.empty_like(cos_rows)
         ops.rope_rows(cos, sin, cur_rows, cos_rows, sin_rows)
-        x = ops.embed_assemble(toks, src, table, None, None, model.err)
-        for i, (w_in, Wqkv, bqkv, Wo, w_post, Wgu, Wdown) in enumerate(layers):
-            qkv = ops.gemv_rows(x, Wqkv, bias=bqkv, norm_w=w_in, eps=T.eps)      # input_layernorm fused
+
+        def attend(i, qkv):
             q, k, v = ops.qkv_split(qkv, 1, R, nq, nkv, hd, hd, cos_rows, sin_rows)   # row r rotated by its position
-            o = ops.attn_extend(q[0], k[0], v[0], kc[i, b0:b1], vc[i, b0:b1], row_start, base, hd)
-            x_mid = ops.gemv_rows(o, Wo, residual=x)
-            a = ops.gemv_rows(x_mid, Wgu, swiglu_inter=T.inter, norm_w=w_post, eps=T.eps)  # post_attention_layernorm
-            x = ops.gemv_rows(a, Wdown, residual=x_mid)
+            return ops.attn_extend(q[0], k[0], v[0], kc[i, b0:b1], vc[i, b0:b1], row_start, base, hd)
+
+        x = _layer_pass(ops.embed_assemble(toks, src, table, None, None, model.err), layers, ops.gemv_rows, attend)
         last.append(x.index_select(0, (row_start[1:] - 1).long()))   # each question's last suffix row
         b0 = b1
     xl = last[0] if len(last) == 1 else torch.cat(last)
-    hn, _, _ = ops.norm_fwd(xl, P[lp + "norm.weight"], None, T.eps, rms=True, save_stats=False)
+    hn = _final_norm(model, xl)
     cur = torch.tensor(Ls, dtype=torch.int32, device=dev)
-    if allowed is None:
-        lg = ops.gemv_batch(hn, model.lm_head_weight())
-    else:
-        lg = allowed.head(hn, model.lm_head_weight(), batch=True)
-    if samp is not None:
-        samp.draw(allowed, lg, seq, cur, repetition_penalty, no_repeat_ngram_size)   # seq[b, L_b]; cur = L_b + 1
-    elif allowed is None:
-        ops.gen_select_batch(lg, seq, cur, repetition_penalty, no_repeat_ngram_size)   # seq[b, L_b]; cur = L_b + 1
-    else:
-        allowed.select(lg, seq, cur, repetition_penalty, no_repeat_ngram_size)
-    steps = [[lg[b:b + 1]] if return_logits else [] for b in range(nb)]
-    outs, steps = _decode_rows(model, kc, vc, seq, Ls, steps, max_new_tokens, repetition_penalty,
-                               no_repeat_ngram_size, eos, return_logits, graph, k_stop, stats, allowed, samp)
+    lg = run.chooser.head(hn, batch=True)
+    run.chooser.choose(lg, seq, cur)   # seq[b, L_b]; cur = L_b + 1
+    steps = [[lg[b:b + 1]] if run.return_logits else [] for b in range(nb)]
+    outs, steps = _decode_rows(model, kc, vc, seq, Ls, steps, run)
     return outs, steps, carry

@@ -852,20 +852,27 @@ def attn_decode_batch(q: torch.Tensor, k_new: torch.Tensor, v_new: torch.Tensor,
     return out
 
 
+def _chooser_rows(who: str, nb: int, seq: torch.Tensor, cur: torch.Tensor, out) -> None:
+    """The rows of the three batched choosers: seq int64 [nb, smax], cur int32 [nb], out (optional) int64 [nb]."""
+    _require(seq, torch.int64, f"{who}.seq")
+    _require(cur, torch.int32, f"{who}.cur")
+    if seq.dim() != 2 or seq.shape[0] != nb or not seq.is_contiguous() or cur.numel() != nb or not cur.is_contiguous():
+        raise RuntimeError(f"{who}: seq contiguous [nb, smax], cur contiguous [nb]")
+    if out is not None:
+        _require(out, torch.int64, f"{who}.out")
+        if out.numel() != nb or not out.is_contiguous():
+            raise RuntimeError(f"{who}: out must be a contiguous [nb] tensor")
+
+
 def gen_select_batch(logits: torch.Tensor, seq: torch.Tensor, cur: torch.Tensor, repetition_penalty: float = 1.0,
                      no_repeat_ngram_size: int = 0, out: torch.Tensor | None = None) -> None:
     """gen_select per row (kd_gen_select_batch): logits [nb, V] bf16, seq [nb, smax] int64, cur [nb]
     int32; writes seq[b, cur[b]], out[b] and cur[b] += 1."""
     _require(logits, torch.bfloat16, "gen_select_batch.logits")
-    _require(seq, torch.int64, "gen_select_batch.seq")
-    _require(cur, torch.int32, "gen_select_batch.cur")
+    if logits.dim() != 2 or logits.stride(1) != 1:
+        raise RuntimeError("gen_select_batch: logits must be [nb, V] with a contiguous last dim")
     nb, V = logits.shape
-    if logits.stride(1) != 1 or seq.dim() != 2 or seq.shape[0] != nb or not seq.is_contiguous() or cur.numel() != nb:
-        raise RuntimeError("gen_select_batch: logits [nb, V], seq contiguous [nb, smax], cur [nb]")
-    if out is not None:
-        _require(out, torch.int64, "gen_select_batch.out")
-        if out.numel() != nb or not out.is_contiguous():
-            raise RuntimeError("gen_select_batch: out must be a contiguous [nb] tensor")
+    _chooser_rows("gen_select_batch", nb, seq, cur, out)
     ws = _workspace(("gen_select_batch", _stream()), nb * V, logits.device)
     NV.call("kd_gen_select_batch", logits.data_ptr(), max(logits.stride(0), V), V, seq.data_ptr(), seq.shape[1], nb,
             cur.data_ptr(), float(repetition_penalty), int(no_repeat_ngram_size), ws.data_ptr(), ws.numel(), _ptr(out),
@@ -999,18 +1006,11 @@ def gen_select_ids(scores: torch.Tensor, ids: torch.Tensor, seq: torch.Tensor, c
     int32; writes seq[b, cur[b]], out[b] and cur[b] += 1.  The lowest id wins a tie; token 0 if every
     allowed id is banned."""
     _require(scores, torch.bfloat16, "gen_select_ids.scores")
-    _require(seq, torch.int64, "gen_select_ids.seq")
-    _require(cur, torch.int32, "gen_select_ids.cur")
     A = _gather_ids(ids, "gen_select_ids")
     if scores.dim() != 2 or scores.shape[1] != A or scores.stride(1) != 1:
         raise RuntimeError("gen_select_ids: scores must be [nb, A] with a contiguous last dim")
     nb = scores.shape[0]
-    if seq.dim() != 2 or seq.shape[0] != nb or not seq.is_contiguous() or cur.numel() != nb or not cur.is_contiguous():
-        raise RuntimeError("gen_select_ids: seq contiguous [nb, smax], cur contiguous [nb]")
-    if out is not None:
-        _require(out, torch.int64, "gen_select_ids.out")
-        if out.numel() != nb or not out.is_contiguous():
-            raise RuntimeError("gen_select_ids: out must be a contiguous [nb] tensor")
+    _chooser_rows("gen_select_ids", nb, seq, cur, out)
     NV.call("kd_gen_select_ids", scores.data_ptr(), max(scores.stride(0), A), ids.data_ptr(), A, seq.data_ptr(),
             seq.shape[1], nb, cur.data_ptr(), float(repetition_penalty), int(no_repeat_ngram_size), _ptr(out), _stream())
 
@@ -1028,23 +1028,17 @@ def gen_sample(scores: torch.Tensor, seq: torch.Tensor, cur: torch.Tensor, *, id
     u(seed, streams[b], cur[b]); writes seq[b, cur[b]], out[b], cur[b] += 1 and u_out[b] (fp32, the u
     used).  Row b depends on its own data and stream alone.  -> out."""
     _require(scores, torch.bfloat16, "gen_sample.scores")
-    _require(seq, torch.int64, "gen_sample.seq")
-    _require(cur, torch.int32, "gen_sample.cur")
-    _require(streams, torch.int64, "gen_sample.streams")
     if scores.dim() != 2 or scores.stride(1) != 1:
         raise RuntimeError("gen_sample: scores must be [nb, N] with a contiguous last dim")
     nb, N = scores.shape
     if ids is not None and (_gather_ids(ids, "gen_sample") != N):
         raise RuntimeError("gen_sample: scores must be [nb, A] for ids [A]")
-    if seq.dim() != 2 or seq.shape[0] != nb or not seq.is_contiguous() or cur.numel() != nb or not cur.is_contiguous():
-        raise RuntimeError("gen_sample: seq contiguous [nb, smax], cur contiguous [nb]")
+    _chooser_rows("gen_sample", nb, seq, cur, out)
+    _require(streams, torch.int64, "gen_sample.streams")
     if streams.numel() != nb or not streams.is_contiguous():
         raise RuntimeError("gen_sample: streams must be a contiguous [nb] tensor")
     if out is None:
         out = torch.empty(nb, dtype=torch.int64, device=scores.device)
-    _require(out, torch.int64, "gen_sample.out")
-    if out.numel() != nb or not out.is_contiguous():
-        raise RuntimeError("gen_sample: out must be a contiguous [nb] tensor")
     if u_out is not None:
         _require(u_out, torch.float32, "gen_sample.u_out")
         if u_out.numel() != nb or not u_out.is_contiguous():

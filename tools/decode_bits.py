@@ -1,11 +1,16 @@
 """The bits of the decode path, to compare two builds (a refactor must not change one of them).
     python tools/decode_bits.py dump OUT.npz [--tree DIR]   one call per shape of every decode op (gemv, gemv_batch,
                                                  gemv_rows, attn_decode, attn_decode_batch, attn_extend, gen_select,
-                                                 gen_select_batch, rope_row, rope_rows, gen_finish) on seeded inputs, at
+                                                 gen_select_batch, gemv_gather, gemv_batch_gather, gen_select_ids,
+                                                 gen_sample over the full row and over allowed ids, rope_row,
+                                                 rope_rows, gen_finish) on seeded inputs, at
                                                  the shapes of tests/test_generate*.py and tests/test_decode_edges.py,
                                                  then generate / generate_batch / generate_grouped on the tests' tiny
                                                  student (graph on and off, stop_check_every 0 and 1, no EOS id, the
-                                                 rows' third new tokens as EOS ids, nine ids: the host scan); every
+                                                 rows' third new tokens as EOS ids, nine ids: the host scan; then
+                                                 with allowed_token_ids on the default head and restrict_head=False,
+                                                 do_sample with and without allowed_token_ids, each without an EOS id
+                                                 and with an active stop; generate(fuse_norm=False)); every
                                                  output tensor goes into OUT.npz as raw bytes.  KDSTEP_LIB selects the
                                                  library, --tree the checkout the Python package is imported from
     python tools/decode_bits.py compare A.npz B.npz   same keys, every array byte-identical: prints the first key that
@@ -26,6 +31,14 @@ QUESTIONS = [(1, 1), (63, 2), (64, 17), (60, 10), (200, 40), (65, 1)]   # (base,
 SMAX = 320
 VS = (8197, 151936)
 KW = dict(repetition_penalty=1.2, no_repeat_ngram_size=2)
+AS = (1, 17, 700)                                                         # allowed ids of the gathered head
+SETTINGS = [(0.7, 50, 1.0), (0.7, 64, 0.9), (1.0, 0, 0.9), (1.5, 1000, 1.0), (1.0, 0, 1.0)]   # tests/test_generate_sample.py
+SEED = 0x5EED5EED5EED
+ALLOWED = sorted(set(range(0, 600, 2)) | {151646, 7, 151935})
+SKW = dict(do_sample=True, temperature=0.7, top_k=50, top_p=0.9, seed=SEED)
+MODES = (("allowed", dict(allowed_token_ids=ALLOWED)),
+         ("allowed_full_head", dict(allowed_token_ids=ALLOWED, restrict_head=False)),
+         ("sampled", SKW), ("sampled_allowed", dict(allowed_token_ids=ALLOWED, **SKW)))
 
 
 def compare(a_path, b_path):
@@ -138,6 +151,53 @@ def dump(out_path, tree):
             ops.gen_select_batch(lg[:, :V] if pad else lg[:, :V].contiguous(), s, cur, 1.2, 2, out=o)   # ldl = V + pad
             keep(f"gen_select_batch/V{V}/pad{pad}", s, o, cur)
 
+    # ---- constrained decoding: the gathered lm_head (the real head shape: gemv_gather_supported needs it), the
+    # select among the allowed ids, and the draw over the full row and over the allowed ids
+    V, K = 151936, 896
+    g = torch.Generator().manual_seed(V + K)
+    w, x = rand(g, V, K + 8, scale=0.05)[:, :K], rand(g, max(NBS), K)
+    id_sets = {}
+    for A in AS:
+        pick = torch.randperm(V, generator=g)[:A].tolist() if A > 1 else [V - 1]
+        if A >= 17:
+            pick = ([0, 15, 16, 31, 32, 4095, 4096, V - 17, V - 16, V - 1] + pick)[:A]   # both sides of 16-row tile boundaries
+        id_sets[A] = torch.tensor(sorted(set(pick)), dtype=torch.int32, device=dev)
+        keep(f"gemv_gather/A{A}", ops.gemv_gather(x[:1].contiguous(), w, id_sets[A]))
+        for nb in NBS:
+            keep(f"gemv_batch_gather/A{A}/nb{nb}", ops.gemv_batch_gather(x[:nb].contiguous(), w, id_sets[A]))
+    del w
+
+    def rows_for(g, nb, N, ids):
+        """nb ragged sequences whose tokens hit the row (or the allowed ids), each ending on a repeated bigram head."""
+        lens = [3 + (37 * b) % 200 for b in range(nb)]
+        seq = torch.full((nb, max(lens) + 3), -1, dtype=torch.int64)
+        for b, n in enumerate(lens):
+            sq = torch.randint(0, N, (n,), generator=g)
+            sq = sq if ids is None else ids.cpu().long()[sq]
+            sq[-1] = sq[n // 2]
+            seq[b, :n] = sq
+        return seq.to(dev), torch.tensor(lens, dtype=torch.int32, device=dev)
+
+    ids = id_sets[700]
+    for nb in NBS:
+        g = torch.Generator().manual_seed(700 + nb)
+        sc = rand(g, nb, 700 + 1, scale=3.0)[:, :700]   # ld = A + 1
+        for name, (penalty, ngram) in (("on", (1.2, 2)), ("off", (1.0, 0))):
+            s, cur = rows_for(g, nb, 700, ids)
+            o = torch.full((nb,), -1, dtype=torch.int64, device=dev)
+            ops.gen_select_ids(sc, ids, s, cur, penalty, ngram, out=o)
+            keep(f"gen_select_ids/nb{nb}/{name}", s, o, cur)
+    for N, sample_ids in [(N, None) for N in VS] + [(700, ids)]:
+        g = torch.Generator().manual_seed(N + 1)
+        sc = rand(g, 3, N, scale=4.0)
+        for case, (temperature, top_k, top_p) in enumerate(SETTINGS):
+            s, cur = rows_for(g, 3, N, sample_ids)
+            o = torch.full((3,), -1, dtype=torch.int64, device=dev)
+            u = torch.full((3,), -1.0, dtype=torch.float32, device=dev)
+            ops.gen_sample(sc, s, cur, ids=sample_ids, **KW, temperature=temperature, top_k=top_k, top_p=top_p,
+                           seed=SEED + case, streams=torch.tensor([0, 2 ** 32 + 5, 2 ** 63 - 1], device=dev), out=o, u_out=u)
+            keep(f"gen_sample/N{N}/{'ids' if sample_ids is not None else 'full'}/case{case}", o, u, s, cur)
+
     # ---- RoPE rows and the EOS latch
     g = torch.Generator().manual_seed(5)
     cos, sin = torch.randn(50, 288, generator=g).to(dev), torch.randn(50, 288, generator=g).to(dev)
@@ -197,6 +257,19 @@ def dump(out_path, tree):
                     r = call(eos_token_id=eos, return_logits=True, graph=graph, stop_check_every=k, stats=stats)
                     keep(f"{name}/eos_{eos_name}/graph{int(graph)}/k{k}", *flat(r),
                          torch.tensor([x for f in stats["finished_at"] for x in f], dtype=torch.int64))
+        for mode, kw in MODES:   # constrained and sampled calls, no EOS id and the rows' third new tokens of that mode
+            plain = flat(call(eos_token_id=(), return_logits=False, **kw))
+            mine = sorted({int(o[0, L + 2]) for o, L in zip(plain, Ls)})
+            for eos_name, eos in (("none", ()), ("third", tuple(mine))):
+                for graph in (True, False):
+                    for k in (0, 1):
+                        stats = {}
+                        r = call(eos_token_id=eos, return_logits=True, graph=graph, stop_check_every=k, stats=stats,
+                                 **kw)
+                        keep(f"{name}/{mode}/eos_{eos_name}/graph{int(graph)}/k{k}", *flat(r),
+                             torch.tensor([x for f in stats["finished_at"] for x in f], dtype=torch.int64))
+        if name == "generate":   # the RMSNorm as its own launch: the A/B route of generate() alone
+            keep("generate/fuse_norm0", *flat(call(eos_token_id=(), return_logits=True, fuse_norm=False)))
     torch.cuda.synchronize()
     np.savez(out_path, **out)
     print(f"{out_path}: {len(out)} arrays, {sum(v.size for v in out.values())} bytes")
