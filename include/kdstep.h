@@ -651,6 +651,79 @@ int kd_gen_sample(const void* scores, int64_t ld_scores, int N, const int32_t* i
                   float top_p, uint64_t seed, const int64_t* streams, void* workspace, size_t workspace_bytes,
                   int64_t* out, float* u_out, void* stream);
 
+/* Beam search (num_beams > 1 of generate() / generate_batch() / generate_grouped()): transformers'
+ * GenerationMixin._beam_search with do_sample=False, early_stopping=False, one returned sequence,
+ * per prompt.  Rows are beams: slot p * K + j is beam j of prompt p (K = num_beams), and a prompt's
+ * result does not depend on the other prompts of the call.  Three launches per step, all
+ * stream-ordered without a host sync, with arguments fixed across steps (one captured graph
+ * replays the step), without floating-point atomics, bit-deterministic and batch invariant in the
+ * sense above.  With L the prompt's length, E the EOS ids, M = max(2, 1 + |E|) * K candidates,
+ * max_len = L + max_new, den[g] = (float)(g ^ length_penalty), and a kill value of -1e9:
+ * kd_gen_beam_topk: one workgroup per row b of logits [nb, V] bf16 (rows ld_logits >= V apart,
+ *   1 <= nb <= 16, 1 <= V <= 262144).  lse = log sum exp over every logit of the row that is not
+ *   NaN (the maximum, then an integer sum of floor(exp(s - max) * 2^40): the same bits in any
+ *   order); l_i = s_i - lse in fp32 (correctly rounded); then the processors of kd_gen_select_batch
+ *   applied to l (repetition penalty on the log-probability: l < 0 ? l * p : l / p; the
+ *   no-repeat-n-gram ban: -inf) over the row's seq[b][0 .. cur_dev[b]); with ids (device int32 [A],
+ *   ascending and unique, 1 <= A <= V) every other id at -inf; acc_i = l_i + run_score[b] (fp32,
+ *   correctly rounded); NaN counts as -inf.  cand_score [nb, M] fp32 and cand_tok [nb, M] int32
+ *   receive the row's M (1 <= M <= 72) largest (acc, token) pairs, descending, the lower token
+ *   first among equal acc; an entry at -inf is reported as (-inf, 0), so a row with nothing above
+ *   -inf yields M such entries.  seq and cur_dev are read only.  The per-row lists suffice: the M
+ *   largest of a prompt's K * V pairs lie in the union of its rows' M largest.  workspace (16-byte
+ *   aligned) >= kd_gen_beam_topk_workspace_size(nb, V) bytes (0 for an nb or V out of range).
+ * kd_gen_beam_step: one workgroup per prompt p of P, rows p * K .. p * K + K - 1 (1 <= K <=
+ *   KD_GEN_BEAMS_MAX, K <= M <= 72, P * K <= 64).  A prompt with open[p] == 0 is closed: nothing of
+ *   it changes any more, except parent[p * K + j] = j.  Otherwise, with cur = cur_dev[p * K] (the
+ *   same in its K rows) and L = prompt_len[p]:
+ *   cand[0 .. M): the M largest of the K lists, descending; ties: lower beam, then lower token;
+ *   hit_c = tok_c in E, or cur + 1 >= max_len;
+ *   running: r_c = score_c + (hit_c ? -1e9 : 0); the K largest r (ties: lower c) become the rows:
+ *     seq[p * K + i][L .. cur] = the parent's generated tokens and tok_c, out[] = tok_c, parent[] =
+ *     the parent beam (0 .. K - 1), run_score[] = r_c, cur_dev[] = cur + 1;
+ *   finished: f_c = score_c / den[cur + 1 - L] + 0 + (hit_c and c < K ? 0 : -1e9) (fp32, each
+ *     operation correctly rounded, in this order); the K largest of the K stored hypotheses followed
+ *     by the M candidates (ties: the earlier one) are stored: fin_score [P, K] descending, fin_len
+ *     [P, K] (the hypothesis' length cur + 1 where hit_c and c < K, else 0: unflagged), fin_seq
+ *     [P, K, smax] (row stride smax) the hypothesis' tokens at [L, fin_len);
+ *   then, with cur + 1 the new length: best = run_score[p * K] / den[cur + 1 - L], worst_k = the
+ *     smallest fin_score where fin_len[k] > 0, else -1e9; open[p] = any_k(best > worst_k) and not
+ *     every one of the M candidates was a hit.
+ *   Only positions [L, max_len) of seq and fin_seq rows are touched (the prompt below L is the same
+ *   in every beam: the caller writes it once, into fin_seq too); they are staged in LDS before any
+ *   is rewritten, which bounds K * max_new <= 4096.  A prompt without room (cur - L outside
+ *   [0, max_new), L + max_new > smax) is closed untouched.  live [2] int32: live[0] = the number of
+ *   prompts with open[p] != 0 after the call, the one word the decode loop reads; live[1] is the
+ *   workgroups' arrival counter (an integer ticket: the last to arrive counts), zero between calls.
+ *   The caller initialises run_score = (0, -1e9, ...) per prompt, fin_score = -1e9, fin_len = 0,
+ *   open = 1, live[1] = 0.  den: device fp32 [max_new + 1].  eos_ids_host: n_eos (0 ..
+ *   KD_GEN_EOS_MAX) ids in HOST memory, passed by value as kd_gen_finish passes them (NULL allowed
+ *   for n_eos = 0).  prompt_len: device int32 [P].
+ * kd_kv_beam_reorder: caches [layers, P * K, HKV, smax, hd] bf16 (hd 64 or 128), one launch for all
+ *   layers, K and V: for every position in [prompt_len[p], cur_dev[p * K] - 1) row p * K + j
+ *   receives what row p * K + parent[p * K + j] held (all K vectors of a (layer, kv head, position)
+ *   are read before one is written).  Positions below prompt_len[p] are identical in a prompt's
+ *   rows and are not touched; nothing outside the prompt's own rows and that range is read or
+ *   written; a row with parent == j (so: an identity permutation) moves nothing.  tail_max (>= 1):
+ *   the most positions a prompt can hold behind its prompt, the launch's grid.  Call it behind
+ *   kd_gen_beam_step and before the next step's attention.
+ * All three: null pointers and bad scalars (penalty <= 0, ngram < 0) -> KD_ERR_ARG, sizes out of
+ * range -> KD_ERR_SHAPE, a short workspace -> KD_ERR_WORKSPACE (a misaligned one KD_ERR_ALIGN), all
+ * before any device work. */
+#define KD_GEN_BEAMS_MAX 8
+size_t kd_gen_beam_topk_workspace_size(int nb, int V);
+int kd_gen_beam_topk(const void* logits, int64_t ld_logits, int V, const int32_t* ids, int A, const int64_t* seq,
+                     int smax, int nb, const int32_t* cur_dev, const float* run_score, float repetition_penalty,
+                     int no_repeat_ngram, int M, void* workspace, size_t workspace_bytes, float* cand_score,
+                     int32_t* cand_tok, void* stream);
+int kd_gen_beam_step(const float* cand_score, const int32_t* cand_tok, int M, int K, int P, int64_t* seq, int smax,
+                     int32_t* cur_dev, float* run_score, int64_t* out, int32_t* parent, int64_t* fin_seq,
+                     float* fin_score, int32_t* fin_len, int32_t* open, int32_t* live, const float* den, int max_new,
+                     const int64_t* eos_ids_host, int n_eos, const int32_t* prompt_len, void* stream);
+int kd_kv_beam_reorder(void* k_cache, void* v_cache, int layers, int P, int K, int HKV, int smax, int hd,
+                       const int32_t* parent, const int32_t* cur_dev, const int32_t* prompt_len, int tail_max,
+                       void* stream);
+
 /* --------------------------------------------------------- model runtime ---- */
 /* One LLaVA-OneVision instance (SigLIP -> projector -> anyres pack -> Qwen2 -> lm_head)
  * whose forward and backward layer loops run in the library (SURVEY §8b "teacher forward"

@@ -131,6 +131,7 @@ _vp, _i32, _i64, _sz, _f32, _u64 = C.c_void_p, C.c_int, C.c_int64, C.c_size_t, C
 KD_GEMV_ROWS_MAX = 1024   # include/kdstep.h: rows per kd_gemv_rows / kd_attn_extend call
 KD_GEN_EOS_MAX = 8        # include/kdstep.h: EOS ids per kd_gen_finish call
 KD_GEN_ALLOWED_MAX = 16384   # include/kdstep.h: allowed ids per kd_gen_select_ids call
+KD_GEN_BEAMS_MAX = 8      # include/kdstep.h: beams per prompt of kd_gen_beam_step
 
 SIGNATURES = {
     "kd_abi_version": (_i32, []),
@@ -205,6 +206,12 @@ SIGNATURES = {
     "kd_gen_sample_workspace_size": (_sz, [_i32, _i32]),
     "kd_gen_sample": (_i32, [_vp, _i64, _i32, _vp, _vp, _i32, _i32, _vp, _f32, _i32, _f32, _i32, _f32, _u64, _vp, _vp,
                              _sz, _vp, _vp, _vp]),
+    "kd_gen_beam_topk_workspace_size": (_sz, [_i32, _i32]),
+    "kd_gen_beam_topk": (_i32, [_vp, _i64, _i32, _vp, _i32, _vp, _i32, _i32, _vp, _vp, _f32, _i32, _i32, _vp, _sz, _vp,
+                                _vp, _vp]),
+    "kd_gen_beam_step": (_i32, [_vp, _vp, _i32, _i32, _i32, _vp, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
+                                _i32, _vp, _i32, _vp, _vp]),
+    "kd_kv_beam_reorder": (_i32, [_vp, _vp, _i32, _i32, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _i32, _vp]),
     "kd_image_resize_u8": (_i32, [_vp, _i32, _i32, _vp, _i32, _i32, _vp, _sz, _vp]),
     "kd_anyres_tiles": (_i32, [_vp, _vp, _i32, _i32, _i32, _i32, _i32, _i32, _vp, _vp, _i32, _vp]),
     "kd_anyres_batch_map": (_i32, [_vp, _i32, _i32, _vp, _i32, _vp]),

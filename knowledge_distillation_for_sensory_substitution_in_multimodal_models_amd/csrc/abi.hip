@@ -224,6 +224,24 @@ int kd_gen_sample(const void* scores, int64_t lds, int N, const int32_t* ids, in
     return kd::launch_gen_sample(scores, lds, N, ids, seq, smax, nb, cur, penalty, ngram, temperature, top_k, top_p, seed,
                                  streams, ws, wsb, out, u_out, s);
 }
+size_t kd_gen_beam_topk_workspace_size(int nb, int V) { return kd::gen_beam_topk_ws(nb, V); }
+int kd_gen_beam_topk(const void* logits, int64_t ldl, int V, const int32_t* ids, int A, const int64_t* seq, int smax, int nb,
+                     const int32_t* cur, const float* run_score, float penalty, int ngram, int M, void* ws, size_t wsb,
+                     float* cand_score, int32_t* cand_tok, void* s) {
+    return kd::launch_gen_beam_topk(logits, ldl, V, ids, A, seq, smax, nb, cur, run_score, penalty, ngram, M, ws, wsb,
+                                    cand_score, cand_tok, s);
+}
+int kd_gen_beam_step(const float* cand_score, const int32_t* cand_tok, int M, int K, int P, int64_t* seq, int smax,
+                     int32_t* cur, float* run_score, int64_t* out, int32_t* parent, int64_t* fin_seq, float* fin_score,
+                     int32_t* fin_len, int32_t* open, int32_t* live, const float* den, int max_new,
+                     const int64_t* eos_ids_host, int n_eos, const int32_t* prompt_len, void* s) {
+    return kd::launch_gen_beam_step(cand_score, cand_tok, M, K, P, seq, smax, cur, run_score, out, parent, fin_seq,
+                                    fin_score, fin_len, open, live, den, max_new, eos_ids_host, n_eos, prompt_len, s);
+}
+int kd_kv_beam_reorder(void* kc, void* vc, int layers, int P, int K, int HKV, int smax, int hd, const int32_t* parent,
+                       const int32_t* cur, const int32_t* prompt_len, int tail_max, void* s) {
+    return kd::launch_kv_beam_reorder(kc, vc, layers, P, K, HKV, smax, hd, parent, cur, prompt_len, tail_max, s);
+}
 size_t kd_image_resize_workspace_size(int H, int W, int oh, int ow) { return kd::image_resize_ws(H, W, oh, ow); }
 int kd_image_resize_u8(const uint8_t* in, int H, int W, uint8_t* out, int oh, int ow, void* ws, size_t ws_bytes,
                        void* s) {

@@ -1498,6 +1498,360 @@ __global__ void __launch_bounds__(1024) k_gen_sample(const bf16* __restrict__ sc
     }
 }
 
+// ------------------------------------------------------------ beam search (num_beams > 1) ----
+// transformers' _beam_search (do_sample=False, early_stopping=False) as three launches per step
+// (include/kdstep.h states the semantics): k_gen_beam_topk, one workgroup per beam row, leaves the
+// row's M best accumulated log-probabilities; k_gen_beam_step, one workgroup per prompt, merges its
+// K rows' lists and keeps the running and the finished hypotheses; k_kv_beam_reorder permutes the
+// generated tail of the K/V cache by parent beam.  Rows are beams: slot p * K + j is beam j of
+// prompt p, and nothing a prompt's workgroups compute depends on the other prompts of the call.
+constexpr int BM_M_MAX = 72;   // candidates per row: max(2, 1 + KD_GEN_EOS_MAX) * KD_GEN_BEAMS_MAX
+constexpr float BM_KILL = -1.0e9f;
+
+struct BtLayout {   // one row's workspace of k_gen_beam_topk: the fp32 row of accumulated scores, then the flags
+    size_t npad, flags_off, row_bytes;
+};
+__host__ __device__ inline BtLayout bt_layout(int V) {
+    BtLayout l;
+    l.npad = ((size_t)V + GS_TILE - 1) / GS_TILE * GS_TILE;
+    l.flags_off = l.npad * 4;
+    l.row_bytes = (l.flags_off + l.npad + 255) / 256 * 256;
+    return l;
+}
+
+// f(i, logit i, flags i) over a row, 8 logits and 8 flags per load where both are aligned
+// (k_gen_sample's first pass), GS_UNROLL loads in flight.  FLAGS = false: the flag bytes are not read
+// (f gets 0): the maximum and the Z pass need the logits alone.
+template <bool FLAGS, typename F>
+__device__ __forceinline__ void bt_for_each(const bf16* __restrict__ scores, const uint8_t* __restrict__ flags, int N,
+                                            F f) {
+    const int nt = blockDim.x;
+    const int v8 = (((uintptr_t)scores & 15) == 0 && ((uintptr_t)flags & 7) == 0) ? N >> 3 : 0;
+    for (int base = threadIdx.x; base < v8; base += GS_UNROLL * nt) {
+        bf16x8 lv[GS_UNROLL];
+        u32x2 fv[GS_UNROLL];
+#pragma unroll
+        for (int k = 0; k < GS_UNROLL; ++k) {
+            const int c = min(base + k * nt, v8 - 1);
+            lv[k] = ((const bf16x8*)scores)[c];
+            fv[k] = FLAGS ? ((const u32x2*)flags)[c] : u32x2{0u, 0u};
+        }
+#pragma unroll
+        for (int k = 0; k < GS_UNROLL; ++k) {
+            const int c = base + k * nt;
+            if (c >= v8) continue;
+#pragma unroll
+            for (int e = 0; e < 8; ++e) f(c * 8 + e, (float)lv[k][e], ((e < 4 ? fv[k].x : fv[k].y) >> (8 * (e & 3))) & 255u);
+        }
+    }
+    for (int i = (v8 << 3) + threadIdx.x; i < N; i += nt) f(i, (float)scores[i], FLAGS ? (uint32_t)flags[i] : 0u);
+}
+
+// Row b = blockIdx.x: acc_i = processed(logit_i - lse) + run_score[b] over the full vocabulary, and
+// its M largest (acc, token) pairs, descending, the lower token first among equals.  lse is order
+// free: the row maximum, then the integer sum of floor(exp(s - max) * 2^40) (k_gen_sample's fixed
+// point), so every thread holds the same Z whatever order the waves ran in.  flags: bit 0 / 1 of
+// gen_flags_row, bit 2 = the id is allowed (with ids).  The M-th largest key comes from
+// k_gen_sample's radix select; the entries above it are collected in any order, the entries equal
+// to it in ascending token order until M are held, and a rank sort of the M pairs orders them.
+// An entry at -inf (banned, not allowed, NaN, or a dead row) is reported as (-inf, 0).
+__global__ void __launch_bounds__(1024) k_gen_beam_topk(const bf16* __restrict__ logits_all, int64_t ldl, int V,
+                                                        const int* __restrict__ ids, int A,
+                                                        int64_t* __restrict__ seq_all, int smax,
+                                                        const int* __restrict__ cur_dev,
+                                                        const float* __restrict__ run_score, float penalty, int ngram,
+                                                        int M, unsigned char* __restrict__ ws,
+                                                        float* __restrict__ cand_score, int* __restrict__ cand_tok) {
+    __shared__ u64 hist[GS_COPIES * GS_HLD];
+    __shared__ u64 tot[256];
+    __shared__ u64 sel[4];
+    __shared__ u64 wsum[16];
+    __shared__ float red[16];
+    __shared__ float top_s[BM_M_MAX];
+    __shared__ int top_t[BM_M_MAX];
+    __shared__ int wcnt[16];
+    __shared__ int cnt;
+    const int b = blockIdx.x, lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+    const BtLayout lay = bt_layout(V);
+    const int npad = (int)lay.npad;
+    unsigned char* row = ws + (size_t)b * lay.row_bytes;
+    float* t = (float*)row;
+    uint8_t* flags = row + lay.flags_off;
+    const GenRow r = gen_row(seq_all, smax, cur_dev);
+    const bf16* logits = logits_all + (size_t)b * ldl;
+    gen_flags_row(V, r.seq, r.len, penalty, ngram, flags);
+    if (ids) {
+        for (int i = threadIdx.x; i < A; i += blockDim.x) {
+            const int id = ids[i];
+            if (id >= 0 && id < V) flags[id] |= 4;   // unique ids: one thread per byte
+        }
+        __syncthreads();
+    }
+
+    // ---- the row's logsumexp over every logit that is not NaN
+    float mx = -INFINITY;
+    bt_for_each<false>(logits, flags, V, [&](int, float s, uint32_t) { mx = fmaxf(mx, s); });   // fmaxf drops a NaN
+    mx = block_max<16>(mx, red);
+    const bool dead = !(mx > -INFINITY);   // nothing above -inf: every entry is (-inf, 0)
+    u64 z = 0;
+    if (!dead)
+        bt_for_each<false>(logits, flags, V, [&](int, float s, uint32_t) {
+            if (s == s) z += (u64)((s == mx ? 1.0f : expf(s - mx)) * 1099511627776.0f);
+        });
+    z = gs_wave_sum(z);
+    if (lane == 0) wsum[wv] = z;
+    __syncthreads();
+    z = 0;
+#pragma unroll
+    for (int i = 0; i < 16; ++i) z += wsum[i];
+    // Z >= 2^40 (the maximum weighs 1): log in double, one rounding to fp32, one more for the sum
+    const float lse = dead ? 0.f : __fadd_rn(mx, (float)(log((double)z) - 40.0 * 0.69314718055994530942));
+
+    // ---- acc into the workspace, and the histogram of the keys' top byte
+    const float rs = run_score[b];
+    gs_hist_clear(hist);
+    bt_for_each<true>(logits, flags, V, [&](int i, float s, uint32_t f) {
+        float v = gen_processed(__fsub_rn(s, lse), f, penalty);
+        if (ids && !(f & 4)) v = -INFINITY;
+        v = __fadd_rn(v, rs);
+        if (dead || !(v == v)) v = -INFINITY;   // NaN never wins
+        if (v == 0.f) v = 0.f;                  // -0 and +0 tie: one key
+        t[i] = v;
+        gs_hist_add(hist, gs_key(v) >> 24, 1ull);
+    });
+    for (int i = V + threadIdx.x; i < npad; i += blockDim.x) {   // the padding: -inf
+        t[i] = -INFINITY;
+        gs_hist_add(hist, gs_key(-INFINITY) >> 24, 1ull);
+    }
+    if (threadIdx.x == 0) cnt = 0;
+    u64 kept = 0;
+    // its first barrier publishes t, hist and cnt; npad >= 256 > M entries, so the M-th largest exists
+    const uint32_t thr = gs_radix_select<false>(t, (const u64*)nullptr, npad, (u64)M, hist, tot, sel, kept);
+    const int above = (int)sel[2];   // entries with a key above thr (< M): sel outlives the select until it is rewritten
+    const bool inf_fill = thr == gs_key(-INFINITY);
+
+    // ---- the entries above the cut, in any order (the rank sort below orders them)
+    gs_for_each4(t, npad, [&](int i4, const f32x4& tv) {
+#pragma unroll
+        for (int e = 0; e < 4; ++e)
+            if (gs_key(tv[e]) > thr) {
+                const int s = atomicAdd(&cnt, 1);
+                if (s < BM_M_MAX) {
+                    top_s[s] = tv[e];
+                    top_t[s] = i4 * 4 + e;
+                }
+            }
+    });
+    // ---- the entries at the cut, lowest tokens first, until M are held
+    if (inf_fill) {
+        for (int s = above + threadIdx.x; s < M; s += blockDim.x) {
+            top_s[s] = -INFINITY;
+            top_t[s] = 0;
+        }
+    } else {
+        int filled = above;   // workgroup-uniform
+        for (int c0 = 0; c0 < V && filled < M; c0 += blockDim.x) {
+            const int i = c0 + threadIdx.x;
+            const bool tie = i < V && gs_key(t[i]) == thr;
+            const unsigned long long m = __ballot(tie);
+            if (lane == 0) wcnt[wv] = __popcll(m);
+            __syncthreads();
+            int off = filled, all = 0;
+#pragma unroll
+            for (int w = 0; w < 16; ++w) {
+                if (w < wv) off += wcnt[w];
+                all += wcnt[w];
+            }
+            const int s = off + __popcll(m & ((1ull << lane) - 1ull));
+            if (tie && s < M) {
+                top_s[s] = t[i];
+                top_t[s] = i;
+            }
+            filled += all;
+            __syncthreads();
+        }
+    }
+    __syncthreads();
+    if ((int)threadIdx.x < M) {
+        const int i = threadIdx.x;
+        const float si = top_s[i];
+        const int ti = top_t[i];
+        int rank = 0;
+        for (int j = 0; j < M; ++j) {
+            const float sj = top_s[j];
+            const int tj = top_t[j];
+            rank += (sj > si || (sj == si && (tj < ti || (tj == ti && j < i)))) ? 1 : 0;
+        }
+        cand_score[(size_t)b * M + rank] = si;
+        cand_tok[(size_t)b * M + rank] = ti;
+    }
+}
+
+// Prompt p = blockIdx.x, rows p * K .. p * K + K - 1: everything of a beam-search step behind the
+// per-row lists (include/kdstep.h, kd_gen_beam_step).  Every selection is a rank sort in LDS over at
+// most K * M <= 576 keys with a total order (score, then position), so the result does not depend on
+// the thread schedule.  Only the generated window [L, L + max_new) of a sequence row moves: the
+// prompt below it is the same in every beam.  The windows are staged in LDS (int32) before any row
+// is rewritten, since beams and finished slots are permuted in place.  live[0] = prompts still open,
+// written by the workgroup that arrives last at the counter live[1] (an integer ticket; the open
+// flags cross workgroups through device-scope atomics).
+__global__ void __launch_bounds__(256) k_gen_beam_step(const float* __restrict__ cand_score,
+                                                       const int* __restrict__ cand_tok, int M, int K, int P,
+                                                       int64_t* __restrict__ seq, int smax, int* __restrict__ cur_dev,
+                                                       float* __restrict__ run_score, int64_t* __restrict__ out,
+                                                       int* __restrict__ parent, int64_t* __restrict__ fin_seq,
+                                                       float* __restrict__ fin_score, int* __restrict__ fin_len,
+                                                       int* __restrict__ open, int* __restrict__ live,
+                                                       const float* __restrict__ den, int max_new, GenEos eos,
+                                                       const int* __restrict__ prompt_len) {
+    extern __shared__ int bs_stage[];   // [K, max_new] running windows, then [K, max_new] finished windows
+    __shared__ float cs[KD_GEN_BEAMS_MAX * BM_M_MAX];
+    __shared__ int ct[KD_GEN_BEAMS_MAX * BM_M_MAX];
+    __shared__ float ms[BM_M_MAX], mr[BM_M_MAX], fs[KD_GEN_BEAMS_MAX + BM_M_MAX];
+    __shared__ int mj[BM_M_MAX], mt[BM_M_MAX], mhit[BM_M_MAX], flen[KD_GEN_BEAMS_MAX + BM_M_MAX];
+    __shared__ int new_c[KD_GEN_BEAMS_MAX], new_f[KD_GEN_BEAMS_MAX];
+    const int p = blockIdx.x, b0 = p * K, tid = threadIdx.x, nt = blockDim.x;
+    int* st_run = bs_stage;
+    int* st_fin = bs_stage + K * max_new;
+    const int L = prompt_len[p], cur = cur_dev[b0], n_old = cur - L;
+    bool run = __hip_atomic_load(&open[p], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0;
+    if (run && (L < 0 || n_old < 0 || n_old >= max_new || (int64_t)L + max_new > smax)) {   // no room: close it
+        run = false;
+        if (tid == 0) __hip_atomic_store(&open[p], 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    }
+    if (run) {   // workgroup-uniform
+        const int n = K * M;
+        for (int i = tid; i < n; i += nt) {
+            const float s = cand_score[(size_t)b0 * M + i];
+            cs[i] = s == s ? s : -INFINITY;
+            ct[i] = cand_tok[(size_t)b0 * M + i];
+        }
+        for (int k = tid; k < K; k += nt) {
+            fs[k] = fin_score[b0 + k];
+            flen[k] = fin_len[b0 + k];
+        }
+        for (int i = tid; i < K * n_old; i += nt) {
+            const int j = i / n_old, x = i - j * n_old;
+            st_run[j * max_new + x] = (int)seq[(size_t)(b0 + j) * smax + L + x];
+        }
+        for (int i = tid; i < K * max_new; i += nt) {
+            const int k = i / max_new, x = i - k * max_new;
+            st_fin[i] = (int)fin_seq[(size_t)(b0 + k) * smax + L + x];
+        }
+        __syncthreads();
+        // ---- cand: the M largest of the K lists; ties: lower beam, then lower token = lower index
+        const bool last = cur + 1 >= L + max_new;
+        const float dn = den[n_old + 1];
+        for (int i = tid; i < n; i += nt) {
+            const float si = cs[i];
+            int rank = 0;
+            for (int j = 0; j < n; ++j) rank += (cs[j] > si || (cs[j] == si && j < i)) ? 1 : 0;
+            if (rank < M) {
+                const int tk = ct[i];
+                bool hit = last;
+#pragma unroll
+                for (int e = 0; e < KD_GEN_EOS_MAX; ++e) hit |= e < eos.n && (int64_t)tk == eos.id[e];
+                ms[rank] = si;
+                mj[rank] = i / M;
+                mt[rank] = tk;
+                mhit[rank] = hit;
+                mr[rank] = hit ? __fadd_rn(si, BM_KILL) : si;
+                const bool just = hit && rank < K;
+                // unsat holds on entry (a prompt whose heuristic turned false is closed): + 0
+                fs[K + rank] = __fadd_rn(__fadd_rn(__fdiv_rn(si, dn), 0.f), just ? 0.f : BM_KILL);
+                flen[K + rank] = just ? cur + 1 : 0;
+            }
+        }
+        __syncthreads();
+        // ---- running: the K largest r (ties: lower c); finished: the K largest of fin ++ cands
+        for (int c = tid; c < M; c += nt) {
+            int rank = 0;
+            for (int j = 0; j < M; ++j) rank += (mr[j] > mr[c] || (mr[j] == mr[c] && j < c)) ? 1 : 0;
+            if (rank < K) new_c[rank] = c;
+        }
+        for (int i = tid; i < K + M; i += nt) {
+            int rank = 0;
+            for (int j = 0; j < K + M; ++j) rank += (fs[j] > fs[i] || (fs[j] == fs[i] && j < i)) ? 1 : 0;
+            if (rank < K) new_f[rank] = i;
+        }
+        __syncthreads();
+        // ---- the rows, from the staged windows
+        for (int i = tid; i < K * (n_old + 1); i += nt) {
+            const int k = i / (n_old + 1), x = i - k * (n_old + 1), c = new_c[k];
+            seq[(size_t)(b0 + k) * smax + L + x] = x < n_old ? (int64_t)st_run[mj[c] * max_new + x] : (int64_t)mt[c];
+        }
+        for (int i = tid; i < K * max_new; i += nt) {
+            const int k = i / max_new, x = i - k * max_new, src = new_f[k];
+            if (src == k) continue;   // the slot keeps its hypothesis
+            int v;
+            if (src < K) v = st_fin[src * max_new + x];
+            else v = x < n_old ? st_run[mj[src - K] * max_new + x] : mt[src - K];   // past n_old: never read
+            fin_seq[(size_t)(b0 + k) * smax + L + x] = v;
+        }
+        if (tid < K) {
+            const int c = new_c[tid], src = new_f[tid];
+            out[b0 + tid] = mt[c];
+            parent[b0 + tid] = mj[c];
+            run_score[b0 + tid] = mr[c];
+            cur_dev[b0 + tid] = cur + 1;
+            fin_score[b0 + tid] = fs[src];
+            fin_len[b0 + tid] = flen[src];
+        }
+        if (tid == 0) {
+            bool all_hit = true;
+            for (int c = 0; c < M; ++c) all_hit &= mhit[c] != 0;
+            const float best = __fdiv_rn(mr[new_c[0]], dn);   // den[cur + 1 - L] with the new cur
+            float worst = INFINITY;
+            for (int k = 0; k < K; ++k) worst = fminf(worst, fs[new_f[k]]);
+            bool unsat = false;
+            for (int k = 0; k < K; ++k) unsat |= best > (flen[new_f[k]] > 0 ? worst : BM_KILL);
+            __hip_atomic_store(&open[p], unsat && !all_hit ? 1 : 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        }
+    } else if (tid < K) {
+        parent[b0 + tid] = tid;   // a closed prompt: its rows stay where they are
+    }
+    __syncthreads();
+    if (tid == 0) {
+        __threadfence();
+        if (atomicAdd(&live[1], 1) == P - 1) {   // the last workgroup to arrive counts
+            __threadfence();
+            int n_open = 0;
+            for (int q = 0; q < P; ++q)
+                n_open += __hip_atomic_load(&open[q], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0 ? 1 : 0;
+            live[0] = n_open;
+            live[1] = 0;
+        }
+    }
+}
+
+// Position L_p + blockIdx.x of prompt p = blockIdx.z, (layer, K or V, kv head) = blockIdx.y: beam row j
+// receives the hd-vector of row parent[j].  Thread (j, 16-byte piece) reads before the barrier and
+// writes behind it, so the in-place permutation never reads a vector already replaced.  Positions
+// outside [L_p, cur - 1), an identity permutation and rows with parent[j] == j move nothing.
+__global__ void __launch_bounds__(128) k_kv_beam_reorder(bf16* __restrict__ kc, bf16* __restrict__ vc, int layers,
+                                                         int nb, int HKV, int smax, int hd, int K,
+                                                         const int* __restrict__ parent,
+                                                         const int* __restrict__ cur_dev,
+                                                         const int* __restrict__ prompt_len) {
+    const int p = blockIdx.z, b0 = p * K, L = prompt_len[p];
+    const int pos = L + (int)blockIdx.x;
+    if (L < 0 || pos >= min(cur_dev[b0] - 1, smax)) return;   // workgroup-uniform
+    const int y = blockIdx.y, h = y % HKV, kv = (y / HKV) & 1, layer = y / (2 * HKV);
+    const int pieces = hd >> 3, j = threadIdx.x / pieces, x = threadIdx.x - j * pieces;
+    int src = j;
+    if (j < K) {
+        src = parent[b0 + j];
+        if (src < 0 || src >= K) src = j;
+    }
+    const bool move = j < K && src != j;
+    bf16* base = (kv ? vc : kc) + (((size_t)layer * nb + b0) * HKV + h) * (size_t)smax * hd + (size_t)pos * hd + x * 8;
+    const size_t row = (size_t)HKV * smax * hd;
+    bf16x8 v = {};
+    if (move) v = *(const bf16x8*)(base + src * row);
+    __syncthreads();
+    if (move) *(bf16x8*)(base + j * row) = v;
+}
+
 }  // namespace
 
 // Launch plan of k_gemv_batch: a function of (N, K) alone.  Never of nb.
@@ -1911,6 +2265,68 @@ int launch_gen_sample(const void* scores, int64_t lds, int N, const int* ids, in
                            (const int*)nullptr, seq, smax, cur_dev, penalty, ngram, temperature, top_k, top_p, seed,
                            streams, (unsigned char*)ws, out, u_out);
     KD_LAUNCH_CHECK("k_gen_sample");
+    return KD_OK;
+}
+
+size_t gen_beam_topk_ws(int nb, int V) {
+    if (nb < 1 || V < 1 || V > GS_N_MAX) return 0;
+    return (size_t)nb * bt_layout(V).row_bytes;
+}
+
+int launch_gen_beam_topk(const void* logits, int64_t ldl, int V, const int* ids, int A, const int64_t* seq, int smax,
+                         int nb, const int* cur_dev, const float* run_score, float penalty, int ngram, int M, void* ws,
+                         size_t ws_bytes, float* cand_score, int* cand_tok, void* stream) {
+    if (int rc = check_chooser_args("gen_beam_topk", logits && seq && cur_dev && run_score && ws && cand_score && cand_tok,
+                                    V, GS_N_MAX, "1 <= V <= 262144", ldl, smax, nb, penalty, ngram))
+        return rc;
+    KD_CHECK_SHAPE(M >= 1 && M <= BM_M_MAX, "gen_beam_topk: 1 <= M <= 72");
+    KD_CHECK_SHAPE(!ids || (A >= 1 && A <= V), "gen_beam_topk: with ids, 1 <= A <= V");
+    if (ws_bytes < gen_beam_topk_ws(nb, V))
+        return fail(KD_ERR_WORKSPACE, "gen_beam_topk: workspace smaller than kd_gen_beam_topk_workspace_size");
+    KD_CHECK_ALIGN(ws, 16, "gen_beam_topk: workspace must be 16-byte aligned");
+    hipLaunchKernelGGL(k_gen_beam_topk, dim3(nb), dim3(1024), 0, as_stream(stream), (const bf16*)logits, ldl, V, ids, A,
+                       const_cast<int64_t*>(seq), smax, cur_dev, run_score, penalty, ngram, M, (unsigned char*)ws,
+                       cand_score, cand_tok);
+    KD_LAUNCH_CHECK("k_gen_beam_topk");
+    return KD_OK;
+}
+
+int launch_gen_beam_step(const float* cand_score, const int* cand_tok, int M, int K, int P, int64_t* seq, int smax,
+                         int* cur_dev, float* run_score, int64_t* out, int* parent, int64_t* fin_seq, float* fin_score,
+                         int* fin_len, int* open, int* live, const float* den, int max_new, const int64_t* eos_ids_host,
+                         int n_eos, const int* prompt_len, void* stream) {
+    KD_CHECK_ARG(cand_score && cand_tok && seq && cur_dev && run_score && out && parent && fin_seq && fin_score &&
+                     fin_len && open && live && den && prompt_len && (eos_ids_host || n_eos == 0),
+                 "gen_beam_step: null pointer");
+    KD_CHECK_SHAPE(K >= 1 && K <= KD_GEN_BEAMS_MAX && M >= K && M <= BM_M_MAX,
+                   "gen_beam_step: 1 <= K <= KD_GEN_BEAMS_MAX, K <= M <= 72");
+    KD_CHECK_SHAPE(P >= 1 && P * K <= 64, "gen_beam_step: P >= 1 and P * K <= 64 rows");
+    KD_CHECK_SHAPE(n_eos >= 0 && n_eos <= KD_GEN_EOS_MAX, "gen_beam_step: 0 <= n_eos <= KD_GEN_EOS_MAX");
+    const size_t lds = (size_t)2 * K * (max_new > 0 ? max_new : 0) * sizeof(int);
+    KD_CHECK_SHAPE(smax > 0 && max_new >= 1 && max_new <= smax && lds <= 32768,
+                   "gen_beam_step: 1 <= max_new <= smax and K * max_new <= 4096 (the windows are staged in LDS)");
+    GenEos eos;
+    for (int e = 0; e < KD_GEN_EOS_MAX; ++e) eos.id[e] = e < n_eos ? eos_ids_host[e] : 0;
+    eos.n = n_eos;
+    hipLaunchKernelGGL(k_gen_beam_step, dim3(P), dim3(256), lds, as_stream(stream), cand_score, cand_tok, M, K, P, seq,
+                       smax, cur_dev, run_score, out, parent, fin_seq, fin_score, fin_len, open, live, den, max_new, eos,
+                       prompt_len);
+    KD_LAUNCH_CHECK("k_gen_beam_step");
+    return KD_OK;
+}
+
+int launch_kv_beam_reorder(void* kc, void* vc, int layers, int P, int K, int HKV, int smax, int hd, const int* parent,
+                           const int* cur_dev, const int* prompt_len, int tail_max, void* stream) {
+    KD_CHECK_ARG(kc && vc && parent && cur_dev && prompt_len, "kv_beam_reorder: null pointer");
+    KD_CHECK_SHAPE(hd == 64 || hd == 128, "kv_beam_reorder: head dim 64 or 128");
+    KD_CHECK_SHAPE(K >= 1 && K <= KD_GEN_BEAMS_MAX && P >= 1 && P * K <= 64,
+                   "kv_beam_reorder: 1 <= K <= KD_GEN_BEAMS_MAX, P >= 1, P * K <= 64 rows");
+    KD_CHECK_SHAPE(layers >= 1 && HKV >= 1 && (int64_t)layers * 2 * HKV <= 65535 && smax > 0 && tail_max >= 1 &&
+                       tail_max <= smax,
+                   "kv_beam_reorder: layers, HKV positive (layers * 2 * HKV <= 65535), 1 <= tail_max <= smax");
+    hipLaunchKernelGGL(k_kv_beam_reorder, dim3(tail_max, layers * 2 * HKV, P), dim3(128), 0, as_stream(stream), (bf16*)kc,
+                       (bf16*)vc, layers, P * K, HKV, smax, hd, K, parent, cur_dev, prompt_len);
+    KD_LAUNCH_CHECK("k_kv_beam_reorder");
     return KD_OK;
 }
 

@@ -110,6 +110,16 @@ size_t gen_sample_ws(int nb, int N);
 int launch_gen_sample(const void* scores, int64_t lds, int N, const int* ids, int64_t* seq, int smax, int nb,
                       int* cur_dev, float penalty, int ngram, float temperature, int top_k, float top_p, uint64_t seed,
                       const int64_t* streams, void* ws, size_t ws_bytes, int64_t* out, float* u_out, void* stream);
+size_t gen_beam_topk_ws(int nb, int V);
+int launch_gen_beam_topk(const void* logits, int64_t ldl, int V, const int* ids, int A, const int64_t* seq, int smax,
+                         int nb, const int* cur_dev, const float* run_score, float penalty, int ngram, int M, void* ws,
+                         size_t ws_bytes, float* cand_score, int* cand_tok, void* stream);
+int launch_gen_beam_step(const float* cand_score, const int* cand_tok, int M, int K, int P, int64_t* seq, int smax,
+                         int* cur_dev, float* run_score, int64_t* out, int* parent, int64_t* fin_seq, float* fin_score,
+                         int* fin_len, int* open, int* live, const float* den, int max_new, const int64_t* eos_ids_host,
+                         int n_eos, const int* prompt_len, void* stream);
+int launch_kv_beam_reorder(void* kc, void* vc, int layers, int P, int K, int HKV, int smax, int hd, const int* parent,
+                           const int* cur_dev, const int* prompt_len, int tail_max, void* stream);
 int launch_image_resize(const uint8_t* in, int H, int W, uint8_t* out, int oh, int ow, void* ws, size_t ws_bytes,
                         void* stream);
 int launch_anyres_tiles(const uint8_t* base, const uint8_t* resized, int nh, int nw, int bh, int bw, int patch,

@@ -86,6 +86,61 @@ or a one-element sequence); the default is the prompt's index in the call (gener
 the flattened question order; generate(): 0), so row r alone with sample_streams=[r] reproduces row
 r of the batch.  A bad temperature, top_k, top_p, seed or sample_streams raises ValueError before any
 device work.  return_logits gives the raw rows, as in the greedy call.
+
+Beam search.  num_beams = K > 1 (default 1: today's call, launch for launch and bit for bit; length_penalty and
+early_stopping are then ignored) is transformers 5.x GenerationMixin._beam_search with do_sample=False,
+early_stopping=False and one returned sequence, per prompt; prompts never interact.  With L the prompt's length, E
+the EOS ids, M = max(2, 1 + |E|) * K, max_len = L + max_new_tokens and den[g] = float32(g ** length_penalty):
+
+    run_seq[K] = prompt; run_score = [0, -1e9, ...] (fp32); fin_score[K] = -1e9; fin_flag[K] = False
+    unsat = True; cur = L
+    loop:
+      for beam j: l = log_softmax(fp32(logits_j)) over the FULL vocabulary
+                  l = no-repeat-ngram(repetition_penalty(l))   # on log-probs (l < 0: l * p), over run_seq[j]
+                  l = -inf outside allowed_token_ids (if given)
+                  acc_j = l + run_score[j]                       (fp32)
+      cand[0..M) = the M largest of acc over (j, token), descending; ties: lower j, then lower token
+      seq_c = run_seq[j_c] + [tok_c];  hit_c = tok_c in E  or  cur + 1 >= max_len
+      running: r_c = score_c + (hit_c ? -1e9 : 0) (fp32); the K largest r (ties: lower c) become run_seq / run_score
+      finished: just_c = hit_c and c < K
+                f_c = score_c / den[cur + 1 - L] + (unsat ? 0 : -1e9) + (just_c ? 0 : -1e9)   (fp32, in this order)
+                fin = the K largest of (fin ++ cands) by score; ties: earlier in that concatenation; the flag travels
+      cur += 1
+      best = run_score[0] / den[cur - L];  worst_k = fin_flag[k] ? min(fin_score) : -1e9
+      unsat = unsat and any_k(best > worst_k)
+      stop when not unsat, or when every one of the M candidates was a hit
+    result: fin_seq[0] (its EOS included if it ended on one), sequences_score = fin_score[0]
+
+torch.topk leaves ties unspecified; the tie rules above are this project's.  A NaN logit counts as -inf, and a
+candidate at -inf carries token 0.  A prompt whose search has stopped is closed: its finished set never changes
+again, and what its rows hold afterwards is unspecified.  tests/beam_ref.py restates this in NumPy and is checked
+against transformers' own generate(num_beams=...).
+  - Rows are beams: a chunk holds MAX_BATCH // K prompts (questions for generate_grouped()) in slots p * K + j.  Each
+    prompt is prefilled once, exactly as without beams; its cache, ids and logits row are copied into its K rows (the
+    first choice sees K equal rows, and run_score kills beams 1 .. K - 1).  generate_grouped() runs its extend pass
+    once per question and copies the suffix K/V along.  generate(num_beams=K) takes the batched route and is
+    generate_batch([prompt], num_beams=K)[0], bit for bit (fuse_norm does not apply there).
+  - A step is the batched decode step with three launches in place of the select: kd_gen_beam_topk (per row the M
+    best accumulated log-probabilities), kd_gen_beam_step (per prompt: the candidates, the running and the finished
+    hypotheses, the reorder of the ids by parent, the heuristic) and kd_kv_beam_reorder (the generated tail of the
+    K/V cache permuted by parent), all with fixed arguments, so the step still replays from one captured graph.
+    max_new_tokens * K <= 4096 (kd_gen_beam_step stages the generated windows in LDS; ValueError otherwise).
+  - allowed_token_ids works, but the full head always runs (the log-softmax is over the whole vocabulary, as
+    transformers computes it before the user's mask); restrict_head=True raises ValueError.  So do do_sample=True,
+    early_stopping other than False, a length_penalty that is not finite, num_beams outside [1, KD_GEN_BEAMS_MAX] and
+    more than KD_GEN_EOS_MAX EOS ids, all before any device work.
+  - The early stop reads one int32, the number of prompts still open, which kd_gen_beam_step writes; it is active
+    whenever stop_check_every > 0 (the heuristic needs no EOS id).  steps_run / checks as without beams;
+    finished_at is the returned length.
+  - stats additionally receives, per chunk: sequences_scores (one float per prompt: fin_score[0]) and the replay
+    trace beam_tokens, beam_parents, beam_scores: per choice (the prefill's first) a [prompts][K] nest of the tokens
+    appended, the parent beam (0 .. K - 1) of each new beam and the running scores.  Entries of a prompt behind the
+    choice that closed it are unspecified.  The trace costs three small device copies per step (between two
+    replays, no host sync), made only when stats is given: the step times of profiles/generate_beams are without.
+  - return_logits gives, per prompt, one [K, V] bf16 tensor per choice of its chunk: the rows that fed that choice
+    (the first: K copies of the prefill's row); those behind the prompt's last choice are unspecified.
+  - A prompt's tokens and score do not depend on the other prompts of the call, on its slot, on the chunking, on
+    graph or on stop_check_every.
 """
 from __future__ import annotations
 
@@ -96,7 +151,7 @@ import typing
 import torch
 
 from . import ops
-from ._native import KD_GEMV_ROWS_MAX, KD_GEN_ALLOWED_MAX, KD_GEN_EOS_MAX
+from ._native import KD_GEMV_ROWS_MAX, KD_GEN_ALLOWED_MAX, KD_GEN_BEAMS_MAX, KD_GEN_EOS_MAX
 
 
 EOS_TOKEN_IDS = (151645,)   # <|im_end|>: generation_config.eos_token_id of the -ov-hf chat checkpoints
@@ -127,17 +182,22 @@ class _Stop:
     """The early stop of one decode loop: kd_gen_finish keeps, on the device, every row's length at
     its first EOS (fin) and the number of rows still running (live); the loop reads live every k
     steps and ends once it is 0.  Inactive (k = 0, no EOS id, or more ids than kd_gen_finish takes)
-    it launches and reads nothing: the loop is then the plain max_new_tokens one."""
+    it launches and reads nothing: the loop is then the plain max_new_tokens one.  With beams (a
+    _BeamRows) live is the number of prompts still open, which kd_gen_beam_step itself writes: mark()
+    launches nothing, and the stop is active whenever k > 0 (the heuristic needs no EOS id)."""
 
-    def __init__(self, model, nb: int, eos, k: int):
-        self.k, self.checks = k, 0
+    def __init__(self, model, nb: int, eos, k: int, beam=None):
+        self.k, self.checks, self.beam = k, 0, beam
         self.ids = sorted(eos)
-        self.active = k > 0 and 0 < len(self.ids) <= KD_GEN_EOS_MAX
+        self.active = k > 0 and (beam is not None or 0 < len(self.ids) <= KD_GEN_EOS_MAX)
         if not self.active:
             return
         dev = model.device
-        self.fin = torch.zeros(nb, dtype=torch.int32, device=dev)
-        self.live = torch.zeros(1, dtype=torch.int32, device=dev)
+        if beam is None:
+            self.fin = torch.zeros(nb, dtype=torch.int32, device=dev)
+            self.live = torch.zeros(1, dtype=torch.int32, device=dev)
+        else:
+            self.live = beam.live[:1]
         cached = getattr(model, "_gen_stop_host", None)   # one pinned word and its event per model
         if cached is None:
             cached = (torch.zeros(1, dtype=torch.int32).pin_memory(), torch.cuda.Event())
@@ -146,7 +206,7 @@ class _Stop:
 
     def mark(self, tok, cur):
         """Behind a select (also inside the captured step: its arguments never change)."""
-        if self.active:
+        if self.active and self.beam is None:
             ops.gen_finish(tok, cur, self.ids, self.fin, self.live)
 
     def done(self, ran: int, n_steps: int) -> bool:
@@ -261,13 +321,125 @@ class _Sampler:
         self.seed, self.streams = int(seed), [int(v) for v in streams]
 
 
+BEAM_KILL = -1.0e9   # transformers' score of a beam that must not be chosen
+BEAM_WINDOW = 4096   # include/kdstep.h, kd_gen_beam_step: K * max_new, the generated windows it stages in LDS
+
+
+class _Beams:
+    """The beam-search settings of one call (num_beams > 1), validated once, before any device work (_beams())."""
+
+    def __init__(self, num_beams: int, length_penalty: float, eos: set):
+        self.K, self.length_penalty, self.eos = num_beams, float(length_penalty), sorted(eos)
+        self.M = max(2, 1 + len(self.eos)) * num_beams   # candidates per step, as transformers takes them
+
+    def den(self, max_new: int) -> list:
+        """den[g] = g ** length_penalty (Python double; the kernel holds it as fp32), g = 0 unused."""
+        return [1.0] + [float(g) ** self.length_penalty for g in range(1, max_new + 1)]
+
+
+def _beams(who: str, num_beams, length_penalty, early_stopping, do_sample, restrict_head, eos_token_id, max_new_tokens):
+    """num_beams == 1 -> None (the other two arguments are ignored); else the call's _Beams, or ValueError."""
+    import math
+    import numbers
+    if isinstance(num_beams, bool) or not isinstance(num_beams, numbers.Integral) \
+            or not 1 <= num_beams <= KD_GEN_BEAMS_MAX:
+        raise ValueError(f"{who}: num_beams must be an int in [1, {KD_GEN_BEAMS_MAX}], got {num_beams!r}")
+    if num_beams == 1:
+        return None
+    if isinstance(length_penalty, bool) or not isinstance(length_penalty, numbers.Real) \
+            or not math.isfinite(length_penalty):
+        raise ValueError(f"{who}: length_penalty must be a finite number, got {length_penalty!r}")
+    if early_stopping is not False:
+        raise ValueError(f"{who}: early_stopping must be False (True and 'never' are not built), got {early_stopping!r}")
+    if do_sample:
+        raise ValueError(f"{who}: num_beams > 1 with do_sample=True (beam sampling) is not built")
+    if restrict_head:
+        raise ValueError(f"{who}: num_beams > 1 runs the full head (the log-softmax is over the whole vocabulary): "
+                         f"restrict_head=True cannot hold")
+    eos = _eos_set(eos_token_id)
+    if len(eos) > KD_GEN_EOS_MAX:
+        raise ValueError(f"{who}: num_beams > 1 takes at most {KD_GEN_EOS_MAX} EOS ids, got {len(eos)}")
+    if int(max_new_tokens) * int(num_beams) > BEAM_WINDOW:
+        raise ValueError(f"{who}: num_beams > 1 needs max_new_tokens * num_beams <= {BEAM_WINDOW} (kd_gen_beam_step stages "
+                         f"the generated windows in LDS), got {int(max_new_tokens)} * {int(num_beams)}")
+    return _Beams(int(num_beams), length_penalty, eos)
+
+
+class _BeamRows:
+    """The device state of one chunk's beam search: rows p * K + j are the beams of prompt p.  choose() is the
+    step behind the head: kd_gen_beam_topk, kd_gen_beam_step, kd_kv_beam_reorder, every argument fixed."""
+
+    def __init__(self, beams: _Beams, model, processors, allowed, seq, Ls, max_new: int, kc, vc, trace: bool):
+        dev, K, P = model.device, beams.K, len(Ls)
+        nb = P * K
+        self.beams, self.K, self.P, self.Ls, self.max_new, self.kc, self.vc = beams, K, P, list(Ls), max_new, kc, vc
+        self.processors, self.ids = processors, None if allowed is None else allowed.ids
+        self.run_score = torch.tensor(([0.0] + [BEAM_KILL] * (K - 1)) * P, dtype=torch.float32, device=dev)
+        self.fin_seq = seq.clone()   # the prompts below every hypothesis
+        self.fin_score = torch.full((nb,), BEAM_KILL, dtype=torch.float32, device=dev)
+        self.fin_len = torch.zeros(nb, dtype=torch.int32, device=dev)
+        self.open = torch.ones(P, dtype=torch.int32, device=dev)
+        self.live = torch.tensor([P, 0], dtype=torch.int32, device=dev)
+        self.parent = torch.zeros(nb, dtype=torch.int32, device=dev)
+        self.tok = torch.zeros(nb, dtype=torch.int64, device=dev)
+        self.prompt_len = torch.tensor(self.Ls, dtype=torch.int32, device=dev)
+        self.den = torch.tensor(beams.den(max_new), dtype=torch.float64).to(torch.float32).to(dev)
+        self.cand_score = torch.empty((nb, beams.M), dtype=torch.float32, device=dev)
+        self.cand_tok = torch.empty((nb, beams.M), dtype=torch.int32, device=dev)
+        self.trace = ([], [], []) if trace else None   # per step: tokens, parents, running scores
+
+    def choose(self, scores, seq, cur, out=None):
+        self.tok = self.tok if out is None else out
+        ops.gen_beam_topk(scores, seq, cur, self.run_score, self.beams.M, ids=self.ids,
+                          repetition_penalty=self.processors[0], no_repeat_ngram_size=self.processors[1],
+                          cand_score=self.cand_score, cand_tok=self.cand_tok)
+        ops.gen_beam_step(self.cand_score, self.cand_tok, self.K, seq, cur, self.run_score, self.tok, self.parent,
+                          self.fin_seq, self.fin_score, self.fin_len, self.open, self.live, self.den, self.beams.eos,
+                          self.prompt_len)
+        ops.kv_beam_reorder(self.kc, self.vc, self.K, self.parent, cur, self.prompt_len, self.max_new)
+
+    def record(self):
+        """Between two steps: what the last one chose (the replay trace of stats)."""
+        if self.trace is not None:
+            for kept, t in zip(self.trace, (self.tok, self.parent, self.run_score)):
+                kept.append(t.clone())
+
+    def results(self, steps, return_logits: bool, stats):
+        """-> (per prompt its best finished hypothesis [1, n], its kept logits rows); the scores and trace into stats."""
+        K, P = self.K, self.P
+        lens = self.fin_len.view(P, K)[:, 0].tolist()
+        if min(lens) < 1:
+            raise RuntimeError("beam search: a prompt ended without a finished hypothesis")
+        if stats is not None:
+            stats["sequences_scores"].append(self.fin_score.view(P, K)[:, 0].tolist())
+            for key, kept in zip(("beam_tokens", "beam_parents", "beam_scores"), self.trace):
+                stats[key].append([t.view(P, K).tolist() for t in kept])
+        outs = [self.fin_seq[p * K, :n].view(1, n) for p, n in enumerate(lens)]
+        return outs, (steps if return_logits else []), lens
+
+
 class _Chooser:
     """The token choice of one call: the one place that knows whether a token is drawn (sampler), taken among the
-    allowed ids (allowed) or the plain argmax, and which head the scores come from.  rows(): one chunk's chooser."""
+    allowed ids (allowed), searched over beams (beams; beam_rows: a chunk's device state) or the plain argmax, and
+    which head the scores come from.  rows(): one chunk's chooser."""
 
-    def __init__(self, model, repetition_penalty, no_repeat_ngram_size, allowed, sampler):
+    def __init__(self, model, repetition_penalty, no_repeat_ngram_size, allowed, sampler, beams=None):
         self.model, self.allowed, self.sampler, self.single, self.streams = model, allowed, sampler, False, None
         self.processors = (repetition_penalty, no_repeat_ngram_size)
+        self.beams, self.beam_rows = beams, None
+
+    def spread(self, kc, vc, seq, Ls, logits, max_new: int, trace: bool):
+        """Beam search behind the prefill: P prompts' caches, ids and logits rows [P, V] copied into their K beam rows,
+        and the first choice made -> (the chunk's chooser, kc, vc, seq of P * K rows, the [P * K, V] rows chosen from)."""
+        K = self.beams.K
+        kc, vc, seq = kc.repeat_interleave(K, dim=1), vc.repeat_interleave(K, dim=1), seq.repeat_interleave(K, dim=0)
+        lg = logits.repeat_interleave(K, dim=0)   # run_score kills beams 1 .. K - 1 of the first choice
+        c = copy.copy(self)
+        c.beam_rows = _BeamRows(self.beams, self.model, self.processors, self.allowed, seq, Ls, max_new, kc, vc, trace)
+        cur = torch.tensor([L for L in Ls for _ in range(K)], dtype=torch.int32, device=self.model.device)
+        c.choose(lg, seq, cur)
+        c.beam_rows.record()
+        return c, kc, vc, seq, lg
 
     def rows(self, lo: int, hi: int, single: bool = False):
         """Prompts [lo, hi) of the call: their stream ids on the device.  single: generate(), plain kd_gen_select."""
@@ -283,12 +455,14 @@ class _Chooser:
         if a is not None and a.gather:
             return ops.gemv_batch_gather(hn, w, a.ids) if batch else ops.gemv_gather(hn, w, a.ids)
         lg = (ops.gemv_batch if batch else ops.gemv)(hn, w)
-        return lg if a is None else a.columns(lg)
+        return lg if a is None or self.beams is not None else a.columns(lg)   # beams: the full row, masked in the kernel
 
     def choose(self, scores, seq, cur, out=None, row=None):
         """Every row's next token from head()'s scores: seq[b, cur[b]], out[b], cur[b] += 1.  row = b: row b alone."""
         a, s = self.allowed, self.sampler
-        if s is not None:   # kd_gen_sample in place of the select of the same scores
+        if self.beam_rows is not None:
+            self.beam_rows.choose(scores, seq, cur, out)
+        elif s is not None:   # kd_gen_sample in place of the select of the same scores
             ops.gen_sample(scores, seq, cur, ids=None if a is None else a.ids, repetition_penalty=self.processors[0],
                            no_repeat_ngram_size=self.processors[1], temperature=s.temperature, top_k=s.top_k,
                            top_p=s.top_p, seed=s.seed, out=out,
@@ -301,7 +475,10 @@ class _Chooser:
             ops.gen_select_batch(scores, seq, cur, *self.processors, out=out)
 
     def first(self, logits, seq_row, L: int, row: int):
-        """The prefill's token from the prompt's full logits row [1, V], into seq_row [1, smax] at L -> the row kept."""
+        """The prefill's token from the prompt's full logits row [1, V], into seq_row [1, smax] at L -> the row kept.
+        Beams: the full row and no token yet (spread() chooses for the whole chunk)."""
+        if self.beams is not None:
+            return logits
         if self.allowed is not None:
             logits = self.allowed.columns(logits)
         if self.allowed is None and self.sampler is None:
@@ -326,17 +503,25 @@ class _Run:
         return dataclasses.replace(self, chooser=self.chooser.rows(lo, hi))
 
 
-def _begin(who: str, model, n_rows: int, stop_check_every, allowed_token_ids, restrict_head, stats, sampling):
-    """The entry points' front matter, every ValueError before any device work: stop_check_every, allowed_token_ids /
-    restrict_head, the stats keys, then sampling = (do_sample, temperature, top_k, top_p, seed, sample_streams) for
-    n_rows prompts (do_sample=False: ignored, as transformers ignores its warpers) -> (k_stop, _Allowed, _Sampler)."""
+def _begin(who: str, model, n_rows: int, stop_check_every, allowed_token_ids, restrict_head, stats, sampling,
+           beam_args=(1, 1.0, False, None, 1)):
+    """The entry points' front matter, every ValueError before any device work: stop_check_every, beam_args =
+    (num_beams, length_penalty, early_stopping, eos_token_id, max_new_tokens), allowed_token_ids / restrict_head, the stats keys,
+    then sampling = (do_sample, temperature, top_k, top_p, seed, sample_streams) for n_rows prompts (do_sample=False:
+    ignored, as transformers ignores its warpers) -> (k_stop, _Allowed, _Sampler, _Beams)."""
     k_stop = _stop_every(stop_check_every, who)
+    beams = _beams(who, *beam_args[:3], sampling[0], restrict_head, *beam_args[3:])
+    if beams is not None and allowed_token_ids is not None:
+        restrict_head = False   # the full head always runs under beams
     allowed = _allowed(model, allowed_token_ids, restrict_head, who)
     _stats_begin(stats)
+    if beams is not None and stats is not None:
+        for key in ("sequences_scores", "beam_tokens", "beam_parents", "beam_scores"):
+            stats[key] = []
     sampler = _Sampler(*sampling[1:], n_rows, who) if sampling[0] else None
     if sampler is not None and stats is not None:
         stats["seed"] = sampler.seed
-    return k_stop, allowed, sampler
+    return k_stop, allowed, sampler, beams
 
 
 class _Layers(typing.NamedTuple):
@@ -454,7 +639,7 @@ def generate(model, input_ids: torch.Tensor, pixel_values: torch.Tensor, image_s
              graph: bool = True, fuse_norm: bool | None = None, stop_check_every: int | None = None,
              stats: dict | None = None, allowed_token_ids=None, restrict_head: bool | None = None,
              do_sample: bool = False, top_k: int = 0, top_p: float = 1.0, seed: int | None = None,
-             sample_streams=None):
+             sample_streams=None, num_beams: int = 1, length_penalty: float = 1.0, early_stopping=False):
     """-> int64 [1, L + n_new] on the device (and the bf16 logits row of every step if
     return_logits).  Greedy unless do_sample (module docstring, "Sampling": temperature, top_k, top_p,
     seed and sample_streams, one int here, then take effect; stats also receives "seed").
@@ -466,12 +651,21 @@ def generate(model, input_ids: torch.Tensor, pixel_values: torch.Tensor, image_s
     stats (a dict) receives one-entry lists steps_run, steps_max, checks (host reads) and finished_at
     ([length at the first EOS, or 0]).
     allowed_token_ids, restrict_head: constrained decoding, see the module docstring (the logits
-    returned are then the compact rows [1, A])."""
+    returned are then the compact rows [1, A]).
+    num_beams > 1 (length_penalty, early_stopping=False): beam search, module docstring; the call is then
+    generate_batch([prompt], ...)[0], bit for bit (fuse_norm does not apply there)."""
     del pad_token_id   # batch of one: no padding of finished rows
-    k_stop, allowed, sampler = _begin("generate", model, 1, stop_check_every, allowed_token_ids, restrict_head, stats,
-                                      (do_sample, temperature, top_k, top_p, seed, sample_streams))
+    sampling = (do_sample, temperature, top_k, top_p, seed, sample_streams)
+    k_stop, allowed, sampler, beams = _begin("generate", model, 1, stop_check_every, allowed_token_ids, restrict_head,
+                                             stats, sampling, (num_beams, length_penalty, early_stopping, eos_token_id, max_new_tokens))
     if input_ids.dim() != 2 or input_ids.shape[0] != 1:
         raise ValueError("generate: batch size 1 (as evaluate_onevision.py runs it)")
+    if beams is not None:   # the batched route: rows are beams
+        got = generate_batch(model, [(input_ids, pixel_values, image_sizes)], max_new_tokens, repetition_penalty,
+                             no_repeat_ngram_size, eos_token_id, None, temperature, return_logits, graph,
+                             stop_check_every, stats, allowed_token_ids, restrict_head, num_beams=num_beams,
+                             length_penalty=length_penalty, early_stopping=early_stopping)
+        return (got[0][0], got[1][0]) if return_logits else got[0]
     chooser = _Chooser(model, repetition_penalty, no_repeat_ngram_size, allowed, sampler).rows(0, 1, single=True)
     T = model.cfg.text
     dev = model.device
@@ -533,7 +727,8 @@ def generate_batch(model, prompts, max_new_tokens: int = 32, repetition_penalty:
                    temperature: float | None = None, return_logits: bool = False, graph: bool = True,
                    stop_check_every: int | None = None, stats: dict | None = None, allowed_token_ids=None,
                    restrict_head: bool | None = None, do_sample: bool = False, top_k: int = 0, top_p: float = 1.0,
-                   seed: int | None = None, sample_streams=None):
+                   seed: int | None = None, sample_streams=None, num_beams: int = 1, length_penalty: float = 1.0,
+                   early_stopping=False):
     """generate() for several prompts at once: prompts is a sequence of (input_ids [1, L_i],
     pixel_values [1, P_i, 3, 384, 384], image_sizes [1, 2]), ragged in L_i and P_i (no padding, no
     attention mask) -> list of int64 [1, L_i + n_i] (and, with return_logits, a list per row of the
@@ -552,12 +747,16 @@ def generate_batch(model, prompts, max_new_tokens: int = 32, repetition_penalty:
     first EOS, or 0).  allowed_token_ids, restrict_head: constrained decoding, see the module
     docstring (the logits returned are then the compact rows [1, A]).  do_sample, temperature, top_k,
     top_p, seed, sample_streams (one stream id per prompt; default: its index): module docstring,
-    "Sampling"; a row's tokens depend on its prompt, the settings, seed and its own stream only."""
+    "Sampling"; a row's tokens depend on its prompt, the settings, seed and its own stream only.
+    num_beams = K > 1, length_penalty, early_stopping=False: beam search (module docstring, "Beam search"): rows are
+    beams, a chunk holds MAX_BATCH // K prompts, each result is its prompt's best finished hypothesis; stats also
+    receives sequences_scores and the replay trace; return_logits gives per prompt and step the [K, V] rows."""
     del pad_token_id   # finished rows are cut, not padded
     prompts = list(prompts)
     sampling = (do_sample, temperature, top_k, top_p, seed, sample_streams)
-    k_stop, allowed, sampler = _begin("generate_batch", model, len(prompts), stop_check_every, allowed_token_ids,
-                                      restrict_head, stats, sampling)
+    k_stop, allowed, sampler, beams = _begin("generate_batch", model, len(prompts), stop_check_every, allowed_token_ids,
+                                             restrict_head, stats, sampling,
+                                             (num_beams, length_penalty, early_stopping, eos_token_id, max_new_tokens))
     if not prompts:
         raise ValueError("generate_batch: no prompts")
     if int(max_new_tokens) < 1:
@@ -566,13 +765,23 @@ def generate_batch(model, prompts, max_new_tokens: int = 32, repetition_penalty:
         if ids.dim() != 2 or ids.shape[0] != 1:
             raise ValueError("generate_batch: every prompt's input_ids must be [1, L]")
     run = _Run(int(max_new_tokens), _eos_set(eos_token_id), return_logits, graph, k_stop, stats,
-               _Chooser(model, repetition_penalty, no_repeat_ngram_size, allowed, sampler))
+               _Chooser(model, repetition_penalty, no_repeat_ngram_size, allowed, sampler, beams))
     outs, logs = [], []
-    for c0 in range(0, len(prompts), MAX_BATCH):
-        o, lg = _generate_rows(model, prompts[c0:c0 + MAX_BATCH], run.rows(c0, c0 + MAX_BATCH))
+    chunk = MAX_BATCH // (1 if beams is None else beams.K)   # rows are beams
+    for c0 in range(0, len(prompts), chunk):
+        o, lg = _generate_rows(model, prompts[c0:c0 + chunk], run.rows(c0, c0 + chunk))
         outs += o
         logs += lg
     return (outs, logs) if return_logits else outs
+
+
+def _beam_spread(model, kc, vc, seq, Ls, logits, run: _Run):
+    """Beam search takes over behind the prefill (chooser.spread) -> (run, kc, vc, seq, Ls of the P * K beam rows,
+    steps: per prompt the [K, V] rows of the first choice)."""
+    K = run.chooser.beams.K
+    chooser, kc, vc, seq, lg = run.chooser.spread(kc, vc, seq, Ls, logits, run.max_new_tokens, run.stats is not None)
+    steps = [[lg[p * K:(p + 1) * K]] if run.return_logits else [] for p in range(len(Ls))]
+    return dataclasses.replace(run, chooser=chooser), kc, vc, seq, [L for L in Ls for _ in range(K)], steps
 
 
 def _generate_rows(model, prompts, run: _Run):
@@ -589,6 +798,8 @@ def _generate_rows(model, prompts, run: _Run):
     for b, prompt in enumerate(prompts):
         first, held = _prefill(model, prompt, kc[:, b], vc[:, b], seq[b:b + 1], run.chooser, b)
         steps[b].append(first)
+    if run.chooser.beams is not None:
+        run, kc, vc, seq, Ls, steps = _beam_spread(model, kc, vc, seq, Ls, torch.cat([s[0] for s in steps]), run)
     done = _decode_rows(model, kc, vc, seq, Ls, steps, run)
     del held   # not before the decode is over: see _prefill
     return done
@@ -611,7 +822,8 @@ def _decode_rows(model, kc, vc, seq, Ls, steps, run: _Run):
     tok = torch.stack([seq[b, Ls[b]] for b in range(nb)])   # the tokens being decoded
     cos_rows = torch.empty((nb, cos.shape[1]), dtype=torch.float32, device=dev)
     sin_rows = torch.empty_like(cos_rows)
-    stop = _Stop(model, nb, run.eos, run.k_stop)
+    beam = run.chooser.beam_rows   # beams: rows p * K + j, Ls per row, steps per prompt
+    stop = _Stop(model, nb, run.eos, run.k_stop, beam)
     stop.mark(tok, cur)   # the prefill's tokens
 
     def attend(i, qkv):
@@ -627,12 +839,21 @@ def _decode_rows(model, kc, vc, seq, Ls, steps, run: _Run):
         return lg
 
     def keep(lg):
-        lg = lg.clone()
-        for b in range(nb):
-            steps[b].append(lg[b:b + 1])
+        if run.return_logits:
+            lg = lg.clone()
+            w = 1 if beam is None else beam.K   # beams: a prompt's [K, V] rows
+            for b in range(nb // w):
+                steps[b].append(lg[b * w:(b + 1) * w])
+        if beam is not None:
+            beam.record()
 
     n_steps = run.max_new_tokens - 1
-    ran = _run_steps(step, n_steps, run.graph, stop, keep if run.return_logits else None)
+    ran = _run_steps(step, n_steps, run.graph, stop,
+                     keep if run.return_logits or (beam is not None and beam.trace is not None) else None)
+    if beam is not None:   # per prompt its best finished hypothesis; steps past a prompt's last one are unspecified
+        outs, steps, lens = beam.results(steps, run.return_logits, run.stats)
+        _stats_chunk(run.stats, ran, n_steps, stop.checks, lens)
+        return outs, steps
     # every row is cut after its own first EOS (fin[b]: its length there, 0 if none)
     fin = _first_eos(stop, seq, Ls, run.max_new_tokens, run.eos)
     ends = [fin[b] or L + run.max_new_tokens for b, L in enumerate(Ls)]
@@ -647,7 +868,8 @@ def generate_grouped(model, groups, max_new_tokens: int = 32, repetition_penalty
                      temperature: float | None = None, return_logits: bool = False, graph: bool = True,
                      stop_check_every: int | None = None, stats: dict | None = None, allowed_token_ids=None,
                      restrict_head: bool | None = None, do_sample: bool = False, top_k: int = 0, top_p: float = 1.0,
-                     seed: int | None = None, sample_streams=None):
+                     seed: int | None = None, sample_streams=None, num_beams: int = 1, length_penalty: float = 1.0,
+                     early_stopping=False):
     """generate_batch() for questions grouped by image: groups is a sequence of (pixel_values
     [1, P, 3, 384, 384], image_sizes [1, 2], [input_ids [1, L_q], ...]) -> one list per group of int64
     [1, L_q + n_q] (and, with return_logits, the same nesting of per-step bf16 logits rows).
@@ -672,12 +894,15 @@ def generate_grouped(model, groups, max_new_tokens: int = 32, repetition_penalty
     returned are then the compact rows [1, A]; the head behind the extend pass is gathered too).
     do_sample, temperature, top_k, top_p, seed, sample_streams: module docstring, "Sampling"; one
     stream id per question in the flattened order of the groups (default: that index), and the token
-    behind the extend pass is drawn too."""
+    behind the extend pass is drawn too.  num_beams = K > 1, length_penalty, early_stopping=False: beam search as in
+    generate_batch(); a chunk holds MAX_BATCH // K questions, the extend pass runs once per question and its
+    suffix K/V is copied to the question's other beam rows."""
     del pad_token_id   # finished rows are cut, not padded
     groups = [(px, sizes, list(qs)) for px, sizes, qs in groups]
     sampling = (do_sample, temperature, top_k, top_p, seed, sample_streams)
-    k_stop, allowed, sampler = _begin("generate_grouped", model, sum(len(qs) for _, _, qs in groups), stop_check_every,
-                                      allowed_token_ids, restrict_head, stats, sampling)
+    k_stop, allowed, sampler, beams = _begin("generate_grouped", model, sum(len(qs) for _, _, qs in groups),
+                                             stop_check_every, allowed_token_ids, restrict_head, stats, sampling,
+                                             (num_beams, length_penalty, early_stopping, eos_token_id, max_new_tokens))
     if not groups:
         raise ValueError("generate_grouped: no groups")
     if int(max_new_tokens) < 1:
@@ -705,12 +930,13 @@ def generate_grouped(model, groups, max_new_tokens: int = 32, repetition_penalty
                 raise ValueError(f"generate_grouped: more than {KD_GEMV_ROWS_MAX} tokens after the image")
             items.append((gi, px, sizes, ids, P0))
     run = _Run(int(max_new_tokens), _eos_set(eos_token_id), return_logits, graph, k_stop, stats,
-               _Chooser(model, repetition_penalty, no_repeat_ngram_size, allowed, sampler))
+               _Chooser(model, repetition_penalty, no_repeat_ngram_size, allowed, sampler, beams))
     outs, logs = [[] for _ in groups], [[] for _ in groups]
     carry = (None, None)   # the prefix K/V of the group a chunk ended in: its next chunk reuses them
-    for c0 in range(0, len(items), MAX_BATCH):
-        chunk = items[c0:c0 + MAX_BATCH]
-        o, lg, carry = _generate_grouped_rows(model, chunk, carry, run.rows(c0, c0 + MAX_BATCH))
+    rows = MAX_BATCH // (1 if beams is None else beams.K)   # rows are beams
+    for c0 in range(0, len(items), rows):
+        chunk = items[c0:c0 + rows]
+        o, lg, carry = _generate_grouped_rows(model, chunk, carry, run.rows(c0, c0 + rows))
         for (gi, *_), ob, lb in zip(chunk, o, lg if return_logits else [None] * len(o)):
             outs[gi].append(ob)
             logs[gi].append(lb)
@@ -776,7 +1002,10 @@ def _generate_grouped_rows(model, chunk, carry, run: _Run):
     hn = _final_norm(model, xl)
     cur = torch.tensor(Ls, dtype=torch.int32, device=dev)
     lg = run.chooser.head(hn, batch=True)
-    run.chooser.choose(lg, seq, cur)   # seq[b, L_b]; cur = L_b + 1
-    steps = [[lg[b:b + 1]] if run.return_logits else [] for b in range(nb)]
+    if run.chooser.beams is not None:
+        run, kc, vc, seq, Ls, steps = _beam_spread(model, kc, vc, seq, Ls, lg, run)
+    else:
+        run.chooser.choose(lg, seq, cur)   # seq[b, L_b]; cur = L_b + 1
+        steps = [[lg[b:b + 1]] if run.return_logits else [] for b in range(nb)]
     outs, steps = _decode_rows(model, kc, vc, seq, Ls, steps, run)
     return outs, steps, carry

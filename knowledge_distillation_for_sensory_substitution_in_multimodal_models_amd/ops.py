@@ -1052,3 +1052,91 @@ def gen_sample(scores: torch.Tensor, seq: torch.Tensor, cur: torch.Tensor, *, id
             cur.data_ptr(), float(repetition_penalty), int(no_repeat_ngram_size), float(temperature), int(top_k),
             float(top_p), seed, streams.data_ptr(), ws.data_ptr(), ws.numel(), out.data_ptr(), _ptr(u_out), _stream())
     return out
+
+
+# --------------------------------------------------------------------- beam search ----
+def gen_beam_topk(logits: torch.Tensor, seq: torch.Tensor, cur: torch.Tensor, run_score: torch.Tensor, M: int, *,
+                  ids: torch.Tensor | None = None, repetition_penalty: float = 1.0, no_repeat_ngram_size: int = 0,
+                  cand_score: torch.Tensor | None = None, cand_tok: torch.Tensor | None = None):
+    """Per beam row its M best accumulated log-probabilities (kd_gen_beam_topk): logits [nb, V] bf16, seq
+    [nb, smax] int64 and cur [nb] int32 (read only), run_score [nb] fp32, ids [A] int32 (ascending, unique:
+    every other id at -inf) -> (cand_score [nb, M] fp32 descending, cand_tok [nb, M] int32; the lower token
+    first among equal scores, an entry at -inf reported as (-inf, 0))."""
+    _require(logits, torch.bfloat16, "gen_beam_topk.logits")
+    if logits.dim() != 2 or logits.stride(1) != 1:
+        raise RuntimeError("gen_beam_topk: logits must be [nb, V] with a contiguous last dim")
+    nb, V = logits.shape
+    _chooser_rows("gen_beam_topk", nb, seq, cur, None)
+    _require(run_score, torch.float32, "gen_beam_topk.run_score")
+    if run_score.numel() != nb or not run_score.is_contiguous():
+        raise RuntimeError("gen_beam_topk: run_score must be a contiguous [nb] tensor")
+    A = 0 if ids is None else _gather_ids(ids, "gen_beam_topk")
+    M = int(M)
+    if cand_score is None:
+        cand_score = torch.empty((nb, max(M, 0)), dtype=torch.float32, device=logits.device)
+    if cand_tok is None:
+        cand_tok = torch.empty((nb, max(M, 0)), dtype=torch.int32, device=logits.device)
+    _require(cand_score, torch.float32, "gen_beam_topk.cand_score")
+    _require(cand_tok, torch.int32, "gen_beam_topk.cand_tok")
+    if cand_score.shape != (nb, M) or cand_tok.shape != (nb, M) or not (cand_score.is_contiguous() and cand_tok.is_contiguous()):
+        raise RuntimeError("gen_beam_topk: cand_score and cand_tok must be contiguous [nb, M] tensors")
+    nbytes = int(NV.lib().kd_gen_beam_topk_workspace_size(nb, V))
+    ws = _workspace(("gen_beam_topk", _stream()), nbytes, logits.device)
+    NV.call("kd_gen_beam_topk", logits.data_ptr(), max(logits.stride(0), V), V, _ptr(ids), A, seq.data_ptr(), seq.shape[1],
+            nb, cur.data_ptr(), run_score.data_ptr(), float(repetition_penalty), int(no_repeat_ngram_size), M,
+            ws.data_ptr(), ws.numel(), cand_score.data_ptr(), cand_tok.data_ptr(), _stream())
+    return cand_score, cand_tok
+
+
+def gen_beam_step(cand_score: torch.Tensor, cand_tok: torch.Tensor, K: int, seq: torch.Tensor, cur: torch.Tensor,
+                  run_score: torch.Tensor, out: torch.Tensor, parent: torch.Tensor, fin_seq: torch.Tensor,
+                  fin_score: torch.Tensor, fin_len: torch.Tensor, open_: torch.Tensor, live: torch.Tensor,
+                  den: torch.Tensor, eos_ids, prompt_len: torch.Tensor) -> None:
+    """One beam-search step of every prompt behind gen_beam_topk() (kd_gen_beam_step): rows p * K + j are
+    the beams of prompt p.  cand_* [P * K, M]; seq and fin_seq [P * K, smax] int64; cur, parent, fin_len
+    [P * K] int32; run_score, fin_score [P * K] fp32; out [P * K] int64; open_, prompt_len [P] int32; live
+    [2] int32 (live[0]: prompts still open; live[1]: the kernel's arrival counter, 0 between calls); den
+    [max_new + 1] fp32 (den[g] = g ** length_penalty); eos_ids: 0..KD_GEN_EOS_MAX host ints."""
+    nb, M = cand_score.shape
+    K = int(K)
+    P = nb // max(K, 1)
+    for t, dt, n, name in ((cand_score, torch.float32, nb * M, "cand_score"), (cand_tok, torch.int32, nb * M, "cand_tok"),
+                           (cur, torch.int32, nb, "cur"), (run_score, torch.float32, nb, "run_score"),
+                           (out, torch.int64, nb, "out"), (parent, torch.int32, nb, "parent"),
+                           (fin_score, torch.float32, nb, "fin_score"), (fin_len, torch.int32, nb, "fin_len"),
+                           (open_, torch.int32, P, "open"), (live, torch.int32, 2, "live"),
+                           (prompt_len, torch.int32, P, "prompt_len"), (seq, torch.int64, seq.numel(), "seq"),
+                           (fin_seq, torch.int64, seq.numel(), "fin_seq"), (den, torch.float32, den.numel(), "den")):
+        _require(t, dt, f"gen_beam_step.{name}")
+        if t.numel() != n or not t.is_contiguous():
+            raise RuntimeError(f"gen_beam_step: {name} must be contiguous with {n} elements")
+    if K < 1 or P * K != nb or seq.dim() != 2 or seq.shape[0] != nb or den.numel() < 2:
+        raise RuntimeError("gen_beam_step: rows must be P * K, seq / fin_seq [P * K, smax], den [max_new + 1]")
+    ids = [int(e) for e in eos_ids]
+    host = (C.c_int64 * max(len(ids), 1))(*ids)
+    NV.call("kd_gen_beam_step", cand_score.data_ptr(), cand_tok.data_ptr(), M, K, P, seq.data_ptr(), seq.shape[1],
+            cur.data_ptr(), run_score.data_ptr(), out.data_ptr(), parent.data_ptr(), fin_seq.data_ptr(),
+            fin_score.data_ptr(), fin_len.data_ptr(), open_.data_ptr(), live.data_ptr(), den.data_ptr(), den.numel() - 1,
+            C.addressof(host), len(ids), prompt_len.data_ptr(), _stream())
+
+
+def kv_beam_reorder(k_cache: torch.Tensor, v_cache: torch.Tensor, K: int, parent: torch.Tensor, cur: torch.Tensor,
+                    prompt_len: torch.Tensor, tail_max: int) -> None:
+    """The generated tail of the caches permuted by parent beam, in place (kd_kv_beam_reorder): caches
+    [layers, P * K, HKV, smax, hd] bf16; for every position in [prompt_len[p], cur[p * K] - 1) row p * K + j
+    receives row p * K + parent[p * K + j].  tail_max: the most positions behind a prompt (the grid)."""
+    layers, nb, HKV, smax, hd = k_cache.shape
+    K = int(K)
+    P = nb // max(K, 1)
+    for t, name in ((k_cache, "k_cache"), (v_cache, "v_cache")):
+        _require(t, torch.bfloat16, f"kv_beam_reorder.{name}")
+        if not t.is_contiguous():
+            raise RuntimeError(f"kv_beam_reorder: {name} must be contiguous")
+    for t, n, name in ((parent, nb, "parent"), (cur, nb, "cur"), (prompt_len, P, "prompt_len")):
+        _require(t, torch.int32, f"kv_beam_reorder.{name}")
+        if t.numel() != n or not t.is_contiguous():
+            raise RuntimeError(f"kv_beam_reorder: {name} must be contiguous with {n} elements")
+    if K < 1 or P * K != nb or v_cache.shape != k_cache.shape:
+        raise RuntimeError("kv_beam_reorder: caches [layers, P * K, HKV, smax, hd] of one shape")
+    NV.call("kd_kv_beam_reorder", k_cache.data_ptr(), v_cache.data_ptr(), layers, P, K, HKV, smax, hd, parent.data_ptr(),
+            cur.data_ptr(), prompt_len.data_ptr(), int(tail_max), _stream())

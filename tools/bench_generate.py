@@ -37,7 +37,16 @@ prefill of one 336x336 prompt (L = 1536) + 32 greedy decode steps with the KV ca
                                                  --sample-only skips every other leg; --sample-profile A runs one greedy
                                                  and one sampled 32-token generate_batch() eagerly, then the same pair
                                                  with A allowed ids (0: without), and nothing else: the run to put
-                                                 under a kernel trace"""
+                                                 under a kernel trace
+    python tools/bench_generate.py --beams 4     beam search: generate_batch(num_beams=K) on 16 // K prompts (its K * P
+                                                 rows fill what a greedy step of as many rows takes) against the greedy
+                                                 generate_batch() at K * P rows and at P rows of the same process,
+                                                 eos_token_id=() everywhere; num_beams=1 against the call without the
+                                                 argument, five times each (a --tree without num_beams times its plain
+                                                 calls: the baseline to interleave with).  --beams-only skips every
+                                                 other leg; --beams-profile runs one greedy and one K-beam 32-token
+                                                 generate_batch() eagerly and nothing else: the run to put under a
+                                                 kernel trace"""
 import argparse
 import inspect
 import sys
@@ -66,8 +75,12 @@ ap.add_argument("--sample", action="store_true", help="time do_sample=True again
 ap.add_argument("--sample-only", action="store_true", help="only the --sample legs (and the greedy calls in them)")
 ap.add_argument("--sample-profile", type=int, default=-1, metavar="A",
                 help="one eager greedy and one sampled generate_batch() of --batch rows, then with A allowed ids (0: not)")
+ap.add_argument("--beams", type=int, default=0, metavar="K", help="time generate_batch(num_beams=K) against the greedy calls")
+ap.add_argument("--beams-only", action="store_true", help="only the --beams leg")
+ap.add_argument("--beams-profile", action="store_true",
+                help="one eager greedy and one K-beam generate_batch() of 16 // K prompts, nothing else")
 args = ap.parse_args()
-if args.allowed_only or args.sample_only:
+if args.allowed_only or args.sample_only or args.beams_only:
     args.answer_only, args.answer_tokens = True, 0
 SAMPLE = dict(do_sample=True, temperature=0.7, top_k=50, top_p=0.9, seed=20260101)
 
@@ -128,6 +141,49 @@ if args.sample_profile >= 0:
     torch.cuda.synchronize()
     print(f"eager generate_batch(), nb = {len(prompts)}, 32 new tokens: one greedy call, then one sampled"
           + (f"; then the same pair with {args.sample_profile} allowed ids" if args.sample_profile else ""))
+    sys.exit(0)
+
+if args.beams_profile:
+    K = max(2, args.beams)
+    rows = [synthetic_batch(1, dev, L=1536, seed=s) for s in range(16 // K)]
+    prompts = [(r["depth_input_ids"], r["depth_pixel_values"], r["image_sizes"]) for r in rows]
+    generate_batch(model, prompts, max_new_tokens=32, graph=False, **kw)
+    generate_batch(model, prompts, max_new_tokens=32, graph=False, num_beams=K, **kw)
+    torch.cuda.synchronize()
+    print(f"eager generate_batch(), {len(prompts)} prompts, 32 new tokens: one greedy call, then one with num_beams = {K}")
+    sys.exit(0)
+
+
+def beams_leg(K):
+    """eos_token_id=() everywhere: every call runs n_new - 1 steps (without an EOS id no hypothesis ends early)."""
+    P = 16 // K
+    rows = [synthetic_batch(1, dev, L=1536, seed=s) for s in range(K * P)]
+    ps = [(r["depth_input_ids"], r["depth_pixel_values"], r["image_sizes"]) for r in rows]
+
+    def pair(prompts, **k):
+        t = [best_of(lambda: generate_batch(model, prompts, max_new_tokens=n, **kw, **k)) for n in (32, 96)]
+        return t[0] * 1e3, (t[1] - t[0]) / 64 * 1e3
+
+    has = "num_beams" in inspect.signature(generate_batch).parameters
+    for tag, k in (("without the argument", {}),) + ((("num_beams=1", dict(num_beams=1)),) if has else ()):
+        runs = [pair(ps[:P], **k) for _ in range(5)]
+        print(f"generate_batch, {P} prompts, {tag}, five times: " +
+              "  ".join(f"{t:.2f} ms / step {s_:.3f} ms" for t, s_ in runs) +
+              f"  (32 tokens per call / marginal step 32 -> 96; spread {(max(t for t, _ in runs) / min(t for t, _ in runs) - 1) * 100:.2f} %)")
+    if not has:
+        print("  this tree has no num_beams: its plain calls only (the baseline to interleave with)")
+        return
+    g_p, g_kp = pair(ps[:P]), pair(ps)
+    bm = pair(ps[:P], num_beams=K)
+    print(f"  greedy, {P} rows: {g_p[0]:.2f} ms per call, step {g_p[1]:.3f} ms;  greedy, {K * P} rows: {g_kp[0]:.2f} ms "
+          f"per call, step {g_kp[1]:.3f} ms")
+    print(f"  num_beams = {K}, {P} prompts ({K * P} rows): {bm[0]:.2f} ms per call, step {bm[1]:.3f} ms "
+          f"({(bm[1] - g_kp[1]) * 1e3:+.0f} us, {(bm[1] / g_kp[1] - 1) * 100:+.2f} % against the greedy step at {K * P} rows; "
+          f"{bm[1] / g_p[1]:.2f}x the greedy step at {P} rows)")
+
+
+if args.beams_only:
+    beams_leg(max(2, args.beams))
     sys.exit(0)
 
 t32, t96 = timed(32), timed(96)
@@ -320,3 +376,6 @@ if args.sample or args.sample_only:
     if args.grouped > 0:
         sample_leg(f"generate_grouped Q={args.grouped} ({len(prompts)} prompts)",
                    lambda n, **k: generate_grouped(model, groups, max_new_tokens=n, **kw, **k))
+
+if args.beams > 0:
+    beams_leg(max(2, args.beams))
