@@ -9,18 +9,26 @@
 //          o / do [B, S, H, hd] bf16 (token-major: what o_proj consumes / produces);
 //          lse [B, H, S] fp32 (natural log of sum exp(score)).
 //
-// Forward, default k_attn_fwd32 (per workgroup: 128 query rows of one head, 4 waves x 32
-//   rows, 32x32x16 MFMAs): S^T = K Q^T so each lane pair (l, l ^ 32) owns ONE query's
-//   scores; max / sum are lane-local plus one v_permlane32_swap, the O^T = V^T P^T
-//   accumulator is lane-local per query, and the S accumulator registers ARE the B operand
-//   of the PV MFMA (key order permuted consistently with the V^T fragment read by
-//   ds_read_b64_tr_b16).  k_attn_fwd (16x16x32, 64 rows per workgroup) stays for A/B
-//   (KD_ATTN_FWD_V=16).
-// Backward: dK / dV per 128 keys of one kv head (k_attn_bwd_dkdv2: 4 waves x two 16-key
-//   sub-tiles; head dim 128: k_attn_bwd_dkdv, 64 keys), looping over the group's query heads
-//   and 32-row query tiles: S = Q K^T and dP = dO V^T with the key on the lane, so P / dS
-//   registers feed dV^T += dO^T P and dK^T += Q^T dS directly.  dQ by its own kernel
-//   (k_attn_bwd_dq: S and dP recomputed per query tile, no atomics).
+// What runs where (padded head dim 64 / 96 | 128), in the product library:
+//   forward   k_attn_fwd32, build F32_DMA, at every head dim (per workgroup: 128 query rows of one
+//             head, 4 waves x 32 rows, 32x32x16 MFMAs): S^T = K Q^T so each lane pair (l, l ^ 32)
+//             owns ONE query's scores; max / sum are lane-local plus one v_permlane32_swap, the
+//             O^T = V^T P^T accumulator is lane-local per query, and the S accumulator registers ARE
+//             the B operand of the PV MFMA (key order permuted consistently with the V^T fragment
+//             read by ds_read_b64_tr_b16).
+//   dQ        k_attn_bwd_dq32, build DQ32_PIPE (the forward's 32x32x16 structure, S and dP
+//             recomputed per key tile, no atomics; it also writes delta = rowsum(dO * O))
+//             | k_attn_bwd_dq<.., 2> (16x16x32 MFMAs, 128 query rows per workgroup).
+//   dK / dV   second, per 128 keys of one query head by k_attn_bwd_dkdv2 (4 waves x two 16-key
+//             sub-tiles) | per 64 keys by k_attn_bwd_dkdv, looping over 64-row query tiles: S = Q K^T
+//             and dP = dO V^T with the key on the lane, so P / dS registers feed dV^T += dO^T P and
+//             dK^T += Q^T dS directly.  GQA: fp32 partials per query head, folded over the group by
+//             k_attn_group_sum, or by k_attn_group_sum_qkv into the fused q|k|v gradient.
+// The A/B library (-DKD_AB_BUILD, tools/ab/attention_*.inc) adds, by KD_ATTN_FWD_V / KD_ATTN_BWD_V
+// (FWD_VARIANTS / BWD_VARIANTS at the launchers): the other builds of k_attn_fwd32 (register-staged,
+// stamps, six waves) and of k_attn_bwd_dq32 (unpipelined, timing diagnostics), k_attn_fwd64,
+// k_attn_fwd32p, the round-2 16x16x32 forward k_attn_fwd, the 16x16x32 dQ and the one-sub-tile
+// dK / dV at head dims 64 / 96, and the 32x32x16 k_attn_bwd_dkdv32.
 #include "common.h"
 
 #include <algorithm>
@@ -32,7 +40,6 @@ namespace kd {
 namespace {
 
 typedef __attribute__((address_space(3))) void lds_void_t;
-typedef __attribute__((address_space(3))) bf16x4 lds_bf16x4_t;
 typedef __attribute__((ext_vector_type(2))) float f32x2;
 constexpr uint32_t OOB = 0x80000000u;
 
@@ -81,6 +88,11 @@ __device__ __forceinline__ void gqa_xcd_map(int H, int HKV, int B, int& h, int& 
 }
 
 // 64 rows x HDP of a [S][HDP] head slab -> LDS image [64][RB] with chunk swizzle SW
+// One LDS-DMA loop in four copies (this, stage_kv32, stage_rows_dma, stage_q32: the swizzle and a
+// compile-time HDP / run-time row stride differ). Behind one template (swizzle, stride) the ISA of
+// every caller of the first three changed (profiles/attention_launcher/isa.txt), so each kernel
+// keeps its helper. This one alone has no `rows_valid <= 0 ? 0u` guard on the record's size: a
+// caller must not pass row0 >= S (none does).
 template <int HDP, bool VIMG>
 __device__ __forceinline__ void stage_kv(char* lds, const bf16* slab, int row0, int S, int wid, int lane) {
     constexpr int RB = Geo<HDP>::RB;
@@ -100,34 +112,12 @@ __device__ __forceinline__ void stage_kv(char* lds, const bf16* slab, int row0, 
     }
 }
 
-template <int RB>
-__device__ __forceinline__ bf16x8 k_frag(const char* lds, int row, int chunk) {
-    return *(const bf16x8*)(lds + row * RB + ((chunk ^ swK<RB>(row)) << 4));
-}
-
-// transposed 4-row read: rows r0+q (q = lane-in-group >> 2), cols d0 + 4p .. +3
-template <int RB>
-__device__ __forceinline__ bf16x4 tr_read(const char* lds, int r, int d) {
-    const int c = d >> 3;
-    const char* a = lds + r * RB + ((c ^ swV<RB>(r)) << 4) + ((d & 4) << 1);
-    return __builtin_amdgcn_ds_read_tr16_b64_v4bf16((lds_bf16x4_t*)a);
-}
-
-// The same transposed read through inline asm: with the builtin, hipcc cannot tell it from
-// the in-flight LDS-DMA of the next K/V tile and waits vmcnt(0) before the first one,
-// so the prefetch only overlapped QK^T + softmax, not PV. The caller retires these reads
-// with its own lgkmcnt(0) (+ sched_barrier) before the MFMAs that consume them.
-template <int RB>
-__device__ __forceinline__ bf16x4 tr_read_asm(const char* lds, int r, int d) {
-    const int c = d >> 3;
-    const char* a = lds + r * RB + ((c ^ swV<RB>(r)) << 4) + ((d & 4) << 1);
-    u32x2 v;
-    asm volatile("ds_read_b64_tr_b16 %0, %1" : "=v"(v) : "v"((uint32_t)(uintptr_t)a));
-    return __builtin_bit_cast(bf16x4, v);
-}
-
-// The same read from a precomputed per-lane LDS byte address plus an immediate offset (the
-// buffer / row part of the address is a compile-time constant in the unrolled tile loop).
+// Transposed 4-row read (ds_read_b64_tr_b16) from a precomputed per-lane LDS byte address plus an
+// immediate offset (the buffer / row part of the address is a compile-time constant in the
+// unrolled tile loop). Inline asm: with the builtin, hipcc cannot tell the read from the
+// in-flight LDS-DMA of the next tile and waits vmcnt(0) before the first one, so the prefetch
+// would not overlap the MFMAs. The caller retires these reads with its own lgkmcnt(0)
+// (+ sched_barrier) before the MFMAs that consume them.
 template <int OFF>
 __device__ __forceinline__ bf16x4 tr_read_off(uint32_t addr) {
     u32x2 v;
@@ -243,14 +233,32 @@ template <int HDP> struct Stage {
     }
 };
 
-// ST (diagnostic build, KD_ATTN_FWD_V=34, tools/stamp_attn.py): per-wave s_memtime totals
+// The forward kernels a launch can name; FWD_VARIANTS (at the launcher) maps the KD_ATTN_FWD_V codes
+// to them. Listed in the order in which the launcher names them per (head dim, causal), which is
+// the order of the kernels in the object. The product library runs F32_DMA alone.
+enum FwdBuild {
+    F32_SIX_WAVES,   // k_attn_fwd32 with six waves (NW = 6): 192 query rows per workgroup; head dims 64 / 96
+    F64,             // k_attn_fwd64: two query blocks per wave (A/B library)
+    F32_DMA,         // k_attn_fwd32, K / V tiles by LDS-DMA, four waves: the product kernel
+    F32_REGSTAGE,    // k_attn_fwd32 staging K / V through registers (RS; Stage above)
+    F32P,            // k_attn_fwd32p: sub-tile-pipelined (A/B library)
+    F32_STAMP,       // k_attn_fwd32 with s_memtime stamps (ST; tools/stamp_attn.py): it overwrites Q rows
+    F16_NQ2,         // k_attn_fwd, the round-2 16x16x32 kernel, two query sub-tiles per wave (A/B library)
+    F16_NQ1,         //   ... one sub-tile per wave
+    N_FWD_BUILDS
+};
+
+// The builds of k_attn_fwd32 (fwd32<HD, C, BUILD>() below names the kernel of one):
+// RS (F32_REGSTAGE): register staging, see Stage.
+// ST (F32_STAMP, diagnostic): per-wave s_memtime totals
 // (prologue, tile compute, end-of-tile wait + barrier, epilogue, whole wave, tiles computed)
 // written as uint32 over the wave's own first Q row after its Q fragments are loaded (the
 // tool passes a scratch Q; nothing else reads that row: Q rows belong to one workgroup)
-// NW waves per workgroup (query block of 32 NW rows; NW = 6 forced variant 36 / the host's choice
+// NW waves per workgroup (query block of 32 NW rows; NW = 6 is F32_SIX_WAVES, for
 // where it balances the grid better: SigLIP's 729 queries are 4 blocks of 192 (512 workgroups, one
 // round on 256 CUs x 2) instead of 6 blocks of 128 (768: a second, half-empty round).  Waves 4 and 5
-// stage nothing (the K/V DMA stays on waves 0-3); three waves per SIMD: <= 168 VGPRs.
+// stage nothing (the K/V DMA stays on waves 0-3); three waves per SIMD: <= 168 VGPRs, which head dim
+// 128 does not fit in (it spilled): no six-wave build there.
 template <int HDP, bool CAUSAL, bool RS, bool ST = false, int NW = 4>
 __global__ void __launch_bounds__(64 * NW, NW == 4 ? 2 : 3) k_attn_fwd32(AttnP p) {
     static_assert(NW == 4 || (NW == 6 && !RS && !ST), "k_attn_fwd32: 6 waves only for the LDS-DMA build");
@@ -496,6 +504,15 @@ __global__ void __launch_bounds__(64 * NW, NW == 4 ? 2 : 3) k_attn_fwd32(AttnP p
     }
 }
 
+// k_attn_fwd32 of a named build. (RS, ST, NW) stay the kernel's own template parameters: they are
+// part of its symbol, and the objects are compared byte for byte across launcher changes.
+template <int HDP, bool CAUSAL, FwdBuild BUILD>
+constexpr auto fwd32() {
+    static_assert(BUILD == F32_DMA || BUILD == F32_REGSTAGE || BUILD == F32_STAMP || BUILD == F32_SIX_WAVES,
+                  "not a build of k_attn_fwd32");
+    return k_attn_fwd32<HDP, CAUSAL, BUILD == F32_REGSTAGE, BUILD == F32_STAMP, BUILD == F32_SIX_WAVES ? 6 : 4>;
+}
+
 #ifdef KD_AB_BUILD   // k_attn_fwd64 / k_attn_fwd32p: measured slower; A/B library only
 #include "attention_fwd64_fwd32p.inc"   // tools/ab/attention_fwd64_fwd32p.inc: k_attn_fwd64 / k_attn_fwd32p and the other forward / backward A/B variants
 #endif  // KD_AB_BUILD
@@ -550,24 +567,6 @@ __device__ __forceinline__ void stage_vec64(float* lds, const float* base, int r
     auto rs = rsrc(base + row0, rows_valid <= 0 ? 0u : (uint32_t)(rows_valid * 4));
     __builtin_amdgcn_raw_ptr_buffer_load_lds(rs, (lds_void_t*)lds, 4, lane < rows_valid ? (uint32_t)(lane * 4) : OOB,
                                              0, 0, 0);
-}
-
-// transposed read from a swK-swizzled image (rows r, 4 consecutive cols starting at d)
-template <int RB>
-__device__ __forceinline__ bf16x4 tr_read_k(const char* lds, int r, int d) {
-    const int c = d >> 3;
-    const char* a = lds + r * RB + ((c ^ swK<RB>(r)) << 4) + ((d & 4) << 1);
-    return __builtin_amdgcn_ds_read_tr16_b64_v4bf16((lds_bf16x4_t*)a);
-}
-
-// asm form of tr_read_k (see tr_read_asm): retired by the caller's lgkmcnt(0)
-template <int RB>
-__device__ __forceinline__ bf16x4 tr_read_k_asm(const char* lds, int r, int d) {
-    const int c = d >> 3;
-    const char* a = lds + r * RB + ((c ^ swK<RB>(r)) << 4) + ((d & 4) << 1);
-    u32x2 v;
-    asm volatile("ds_read_b64_tr_b16 %0, %1" : "=v"(v) : "v"((uint32_t)(uintptr_t)a));
-    return __builtin_bit_cast(bf16x4, v);
 }
 
 // dK / dV for 64 keys of ONE query head (4 waves x 16 keys, key on the lane), looping
@@ -1424,12 +1423,6 @@ __device__ __forceinline__ float f32_mul(float a, float b) {
     asm("v_mul_f32 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b));
     return r;
 }
-// s_waitcnt lgkmcnt(0), then every register of `r` named (no use of them above the wait)
-template <int N> __device__ __forceinline__ void wait_lgkm0_all(u32x2 (&r)[N]) {
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-#pragma unroll
-    for (int i = 0; i < N; ++i) asm volatile("" : "+v"(r[i]));
-}
 
 // per-lane byte addresses of the 32x32 transposed reads (the forward's V^T pattern): lane reads
 // rows 4 hf + ((lane >> 2) & 3) (x = 0) and + 8 (x = 1), 4 columns at 32 D + 16 ((lane >> 4) & 1)
@@ -1448,14 +1441,32 @@ __device__ __forceinline__ void tr_addrs32(uint32_t (&ta)[ND][2], uint32_t base,
         }
 }
 
+// The backward kernels a launch can name, dQ and dK / dV; BWD_VARIANTS (at the launcher) pairs them
+// per KD_ATTN_BWD_V code. Listed, as FwdBuild, in the order in which the launcher names them.
+enum DqBuild {
+    DQ32_UNPIPED,   // k_attn_bwd_dq32 without the software pipeline (hd 64: three workgroups per CU)
+    DQ32_DIAG1, DQ32_DIAG2, DQ32_DIAG3, DQ32_DIAG4,   // its timing builds (DIAG below): wrong results by design
+    DQ32_PIPE,      // k_attn_bwd_dq32, interior tiles software-pipelined: the product kernel at head dims 64 / 96
+    DQ16_NQ2,       // k_attn_bwd_dq (16x16x32), two query sub-tiles per wave: the product kernel at head dim 128
+    DQ16_NQ1,       //   ... one sub-tile per wave (A/B library)
+    N_DQ_BUILDS
+};
+enum KvBuild {
+    KV32,   // k_attn_bwd_dkdv32: 32x32x16 MFMAs, 128 keys per workgroup (A/B library)
+    KV1,    // k_attn_bwd_dkdv: one 16-key sub-tile per wave, 64 keys: the product kernel at head dim 128
+    KV2,    // k_attn_bwd_dkdv2: two sub-tiles per wave, 128 keys: the product kernel at head dims 64 / 96
+    N_KV_BUILDS
+};
+
 // dQ for 128 query rows of one head (4 waves x 32 queries), K / V tiles of 64 keys double-
 // buffered by LDS-DMA; also writes delta = rowsum(dO * O) for the dK / dV kernel (launched after)
-// DIAG (A/B library timing diagnostics only; wrong results): 1 = no K/V staging after the first tile
+// Builds (dq32<HD, C, BUILD>() below names the kernel of one):
+// DIAG (DQ32_DIAG1-4, A/B library timing diagnostics only; wrong results): 1 = no K/V staging after the first tile
 // (compute + barriers alone), 2 = staging without the end-of-tile vmcnt / barrier wait, 3 = neither
 // staging nor waits (compute alone), 4 = as 3 with every tile taking the edge path
 // PIPE: interior tiles software-pipelined (softmax in the MFMA gaps; 182 / 236 VGPRs at hd 64 / 96).
-// The product runs it at two workgroups per CU; the unpipelined build (163 VGPRs at hd 64: three per CU)
-// measured equal at hd 96 and 4 % slower at hd 64 (A/B: KD_ATTN_BWD_V=3).
+// The product runs it at two workgroups per CU (DQ32_PIPE); the unpipelined build (DQ32_UNPIPED; 163 VGPRs
+// at hd 64: OCC = three per CU) measured equal at hd 96 and 4 % slower at hd 64 (A/B: KD_ATTN_BWD_V=3).
 template <int HDP, bool CAUSAL, int OCC = 2, int DIAG = 0, bool PIPE = true>
 __global__ void __launch_bounds__(256, OCC) k_attn_bwd_dq32(AttnBwdP p) {
     // hd 128 would need lgkmcnt(16) below (the counter holds 15) and more VGPRs than two waves allow
@@ -1601,7 +1612,7 @@ __global__ void __launch_bounds__(256, OCC) k_attn_bwd_dq32(AttnBwdP p) {
                 part(I1c{}, I0c{}, std::integral_constant<int, 8>{}, std::integral_constant<int, 2 * ND>{}, m_c);
                 __builtin_amdgcn_sched_barrier(0);
             });
-            wait_lgkm0_all(kd);
+            wait_lgkm_n<0>(kd);
             __builtin_amdgcn_sched_barrier(0);
             sfor<ND>([&](auto d_c) {
                 constexpr int d = decltype(d_c)::value;
@@ -1731,160 +1742,199 @@ __global__ void __launch_bounds__(256, OCC) k_attn_bwd_dq32(AttnBwdP p) {
     }
 }
 
+// k_attn_bwd_dq32 of a named build ((OCC, DIAG, PIPE) stay its template parameters: see fwd32())
+template <int HDP, bool CAUSAL, DqBuild BUILD>
+constexpr auto dq32() {
+    static_assert(BUILD <= DQ32_PIPE, "not a build of k_attn_bwd_dq32");
+    constexpr int DIAG = (BUILD >= DQ32_DIAG1 && BUILD <= DQ32_DIAG4) ? BUILD - DQ32_DIAG1 + 1 : 0;
+    return k_attn_bwd_dq32<HDP, CAUSAL, (BUILD == DQ32_UNPIPED && HDP == 64) ? 3 : 2, DIAG, BUILD != DQ32_UNPIPED>;
+}
+
 #ifdef KD_AB_BUILD
 #include "attention_bwd_dkdv32.inc"   // tools/ab/attention_bwd_dkdv32.inc: the 32x32x16 dK / dV kernel (KD_ATTN_BWD_V=32)
 #endif  // KD_AB_BUILD
 
-}  // namespace
+// -------------------------------------------------------------------- launchers ----
+// A launch: the descriptor checks, the variant row of (code, hdp) -- code 0 in the product library;
+// the A/B library reads KD_ATTN_*_V on every call, so a test can switch variants inside one
+// process -- then dispatch() turns (hdp, causal) into template arguments and the lambda launches
+// the row's kernels.
+enum : unsigned { HD_64 = 1, HD_96 = 2, HD_128 = 4, HD_ALL = 7 };
+constexpr unsigned hd_bit(int hdp) { return hdp == 64 ? HD_64 : (hdp == 96 ? HD_96 : HD_128); }
 
-#ifdef KD_AB_BUILD
-// the six-wave forward by default: not yet (A/B with forced variant 36 first); head dim 128
-// needs more than the 168 VGPRs of three waves per SIMD (it spilled), so it keeps four waves
-static bool fwd_nw6(const kd_attn_desc* d) {
-    (void)d;
-    return false;
-}
-template <int HD, bool C>
-void launch_fwd_nw6(dim3 grid, size_t smem, hipStream_t st, const AttnP& p) {
-    if constexpr (HD == 128) {
-        grid.z = (p.S + 127) / 128;
-        hipLaunchKernelGGL((k_attn_fwd32<HD, C, false>), grid, dim3(256), smem, st, p);
-    } else {
-        hipLaunchKernelGGL((k_attn_fwd32<HD, C, false, false, 6>), grid, dim3(384), smem, st, p);
+// the row of `code` at padded head dim hdp; a code with no row there runs code 0's; nullptr: no such code
+template <typename V, size_t N>
+const V* variant_row(const V (&table)[N], int code, int hdp) {
+    bool known = false;
+    for (const V& r : table) {
+        if (r.code != code) continue;
+        if (r.hds & hd_bit(hdp)) return &r;
+        known = true;
     }
+    return known ? variant_row(table, 0, hdp) : nullptr;
+}
+// the A/B library's switches; the product library reads no environment: code 0, no flag
+int env_code(const char* name) {
+#ifdef KD_AB_BUILD
+    const char* e = std::getenv(name);
+    return e ? std::atoi(e) : 0;
+#else
+    return (void)name, 0;
+#endif
+}
+bool env_is_1(const char* name) {
+#ifdef KD_AB_BUILD
+    const char* e = std::getenv(name);
+    return e && e[0] == '1';
+#else
+    return (void)name, false;
+#endif
 }
 
-#endif  // KD_AB_BUILD
+// f(std::integral_constant<int, hdp>, std::bool_constant<causal>) for a checked hdp
+template <typename F>
+int dispatch(int hdp, bool causal, F&& f) {
+    auto with_hd = [&](auto hd) { return causal ? f(hd, std::true_type{}) : f(hd, std::false_type{}); };
+    if (hdp == 64) return with_hd(std::integral_constant<int, 64>{});
+    if (hdp == 96) return with_hd(std::integral_constant<int, 96>{});
+    return with_hd(std::integral_constant<int, 128>{});
+}
+// f(std::integral_constant<int, I>) for I = N-1 .. 0: the launch lambdas walk a build enum with it.
+// Downwards, because hipcc emits the kernels that one instantiation names last-first, and the order
+// of the kernels in the object is held fixed (the build enums list it): a launcher change is
+// checked by comparing the device assembly byte for byte, profiles/attention_launcher/isa.txt.
+template <typename F, int... I>
+void for_each_build(F&& f, std::integer_sequence<int, I...>) {
+    (f(std::integral_constant<int, (int)sizeof...(I) - 1 - I>{}), ...);
+}
+template <int N, typename F>
+void for_each_build(F&& f) { for_each_build(f, std::make_integer_sequence<int, N>{}); }
 
-int launch_attn_fwd(const kd_attn_desc* d, void* stream_) {
-    KD_CHECK_ARG(d && d->q && d->k && d->v && d->o, "attn_fwd: null pointer");
-    KD_CHECK_SHAPE(d->B > 0 && d->S > 0 && d->H > 0 && d->HKV > 0 && d->H % d->HKV == 0, "attn_fwd: heads");
-    KD_CHECK_SHAPE(d->hd > 0 && d->hd <= d->hdp && d->hd % 4 == 0, "attn_fwd: hd");
-    KD_CHECK_SHAPE(d->hdp == 64 || d->hdp == 96 || d->hdp == 128, "attn_fwd: padded head dim must be 64/96/128");
-    KD_CHECK_SHAPE(!(d->hdp == 96 && d->hd > 80) && !(d->hdp == 64 && d->hd > 64), "attn_fwd: hd exceeds tile cover");
-    AttnP p{(const bf16*)d->q, (const bf16*)d->k, (const bf16*)d->v, (bf16*)d->o, d->lse,
-            d->B, d->H, d->HKV, d->S, d->hd, (float)(1.4426950408889634 / std::sqrt((double)d->hd))};
-    hipStream_t st = as_stream(stream_);
-    const int rb = d->hdp == 64 ? 128 : 256;
-    const size_t smem = 2 * 2 * 64 * rb;
-#ifdef KD_AB_BUILD
-    // KD_ATTN_FWD_V (A/B and diagnostics; read per call, so a test can switch variants inside one
-    // process): unset / 32 = k_attn_fwd32 (LDS-DMA staging, the product kernel), 64 = k_attn_fwd64
-    // (two query blocks per wave), 35 = its register-staged build, 33 = the sub-tile-pipelined
-    // k_attn_fwd32p, 34 = the stamp build, 36 = six-wave workgroups, 16 = the 16x16x32 k_attn_fwd
-    // (KD_ATTN_FWD_NQ=1: one query sub-tile per wave)
-    static const int nq = [] { const char* e = std::getenv("KD_ATTN_FWD_NQ"); return (e && e[0] == '1') ? 1 : 2; }();
-    const char* fve = std::getenv("KD_ATTN_FWD_V");
-    const int fv = fve ? std::atoi(fve) : 0;
-    const bool v16 = fv == 16, nw6 = fv == 36, w64 = fv == 64;
-    dim3 grid(d->H, d->B, v16 ? (d->S + 64 * nq - 1) / (64 * nq)
-                              : (w64 ? (d->S + 255) / 256 : (d->S + (nw6 ? 191 : 127)) / (nw6 ? 192 : 128)));
-#define LAUNCH(HD, C)                                                                                \
-    do {                                                                                             \
-        if (nw6) launch_fwd_nw6<HD, C>(grid, smem, st, p);                                           \
-        else if (w64) hipLaunchKernelGGL((k_attn_fwd64<HD, C>), grid, dim3(256), smem, st, p);       \
-        else if (fv == 0 || fv == 32) hipLaunchKernelGGL((k_attn_fwd32<HD, C, false>), grid, dim3(256), smem, st, p); \
-        else if (fv == 35) hipLaunchKernelGGL((k_attn_fwd32<HD, C, true>), grid, dim3(256), smem, st, p); \
-        else if (fv == 33) hipLaunchKernelGGL((k_attn_fwd32p<HD, C>), grid, dim3(256), smem, st, p); \
-        else if (fv == 34) hipLaunchKernelGGL((k_attn_fwd32<HD, C, false, true>), grid, dim3(256), smem, st, p); \
-        else if (nq == 2) hipLaunchKernelGGL((k_attn_fwd<HD, C, 2>), grid, dim3(256), smem, st, p);  \
-        else hipLaunchKernelGGL((k_attn_fwd<HD, C, 1>), grid, dim3(256), smem, st, p);               \
-    } while (0)
-#else
-    const dim3 grid(d->H, d->B, (d->S + 127) / 128);
-#define LAUNCH(HD, C) hipLaunchKernelGGL((k_attn_fwd32<HD, C, false>), grid, dim3(256), smem, st, p)
-#endif
-    if (d->hdp == 64) { if (d->causal) LAUNCH(64, true); else LAUNCH(64, false); }
-    else if (d->hdp == 96) { if (d->causal) LAUNCH(96, true); else LAUNCH(96, false); }
-    else { if (d->causal) LAUNCH(128, true); else LAUNCH(128, false); }
-#undef LAUNCH
-    KD_LAUNCH_CHECK("k_attn_fwd");
+// The checks kd_attn_fwd and kd_attn_bwd share. Order, codes and texts are pinned per entry by
+// tests/golden/attn_reject_table.json: the forward tells "heads" from "hd" and also wants H and hd
+// positive, the backward says "shape" for both.
+int check_attn_shape(const char* who, int B, int S, int H, int HKV, int hd, int hdp) {
+    const bool fwd = std::string(who) == "attn_fwd";
+    auto msg = [who](const char* what) { return std::string(who) + ": " + what; };
+    KD_CHECK_SHAPE(B > 0 && S > 0 && (H > 0 || !fwd) && HKV > 0 && H % HKV == 0, msg(fwd ? "heads" : "shape"));
+    KD_CHECK_SHAPE((hd > 0 || !fwd) && hd <= hdp && hd % 4 == 0, msg(fwd ? "hd" : "shape"));
+    KD_CHECK_SHAPE(hdp == 64 || hdp == 96 || hdp == 128, msg("padded head dim must be 64/96/128"));
+    KD_CHECK_SHAPE(!(hdp == 96 && hd > 80) && !(hdp == 64 && hd > 64), msg("hd exceeds tile cover"));
     return KD_OK;
 }
 
-// dK / dV launch: the two-sub-tile kernel for head dims 64 / 96 (at 128 its 2 x 2 x DT
-// accumulator tiles do not fit beside the fragments: the one-sub-tile kernel there; the 7B
-// teacher never runs a backward)
-template <int HD, bool C>
-void launch_dq1(dim3 grid, size_t smem, hipStream_t st, const AttnBwdP& p) {
+// One row per KD_ATTN_FWD_V code: the kernel, the query rows and threads of a workgroup, the padded
+// head dims that have the build (six waves spill at 128: code 0's four there). A code in no row is
+// KD_ERR_ARG. Code 116: 16 under KD_ATTN_FWD_NQ=1.
+struct FwdVariant { int code; FwdBuild build; int qrows, block; unsigned hds; };
+constexpr FwdVariant FWD_VARIANTS[] = {
+    {0, F32_DMA, 128, 256, HD_ALL},
 #ifdef KD_AB_BUILD
-    hipLaunchKernelGGL((k_attn_bwd_dq<HD, C, 1>), grid, dim3(256), smem, st, p);
+    {32, F32_DMA, 128, 256, HD_ALL},
+    {33, F32P, 128, 256, HD_ALL},
+    {34, F32_STAMP, 128, 256, HD_ALL},
+    {35, F32_REGSTAGE, 128, 256, HD_ALL},
+    {36, F32_SIX_WAVES, 192, 384, HD_64 | HD_96},
+    {64, F64, 256, 256, HD_ALL},
+    {16, F16_NQ2, 128, 256, HD_ALL},
+    {116, F16_NQ1, 64, 256, HD_ALL},
+#endif
+};
+constexpr bool fwd_has(FwdBuild b, int hdp) {
+    for (const FwdVariant& v : FWD_VARIANTS)
+        if (v.build == b && (v.hds & hd_bit(hdp))) return true;
+    return false;
+}
+using FwdKernel = void (*)(AttnP);
+template <int HD, bool C, FwdBuild B>
+constexpr FwdKernel fwd_kernel() {
+#ifdef KD_AB_BUILD   // the kernels of tools/ab/attention_fwd*.inc
+    if constexpr (B == F64) return k_attn_fwd64<HD, C>;
+    else if constexpr (B == F32P) return k_attn_fwd32p<HD, C>;
+    else if constexpr (B == F16_NQ2 || B == F16_NQ1) return k_attn_fwd<HD, C, B == F16_NQ2 ? 2 : 1>;
+    else
+#endif
+    return fwd32<HD, C, B>();
+}
+
+// One row per KD_ATTN_BWD_V code: the dQ kernel (it also writes delta = rowsum(dO * O): its lanes hold
+// the dO rows already) with its query rows per workgroup, and the dK / dV kernel, which reads delta
+// and therefore runs second, with its keys per workgroup; 256 threads each. Head dim 128 has no
+// k_attn_bwd_dq32 (lgkmcnt(16), VGPRs) and no room for dkdv2's 2 x 2 x DT accumulator tiles beside
+// the fragments, so there every code runs the 16x16x32 pair (the 7B teacher never runs a backward).
+// Codes 100 / 102 / 116: 0 (at 128) / 2 / 16 under KD_ATTN_DQ_NQ=1.
+struct BwdVariant { int code; DqBuild dq; int qrows; KvBuild kv; int keys; unsigned hds; };
+constexpr BwdVariant BWD_VARIANTS[] = {
+    {0, DQ32_PIPE, 128, KV2, 128, HD_64 | HD_96},
+    {0, DQ16_NQ2, 128, KV1, 64, HD_128},
+#ifdef KD_AB_BUILD
+    {100, DQ16_NQ1, 64, KV1, 64, HD_128},
+    {16, DQ16_NQ2, 128, KV1, 64, HD_ALL},
+    {2, DQ16_NQ2, 128, KV2, 128, HD_64 | HD_96},   // the round-6 pair
+    {3, DQ32_UNPIPED, 128, KV2, 128, HD_64 | HD_96},
+    {5, DQ32_DIAG1, 128, KV2, 128, HD_64 | HD_96},
+    {6, DQ32_DIAG2, 128, KV2, 128, HD_64 | HD_96},
+    {7, DQ32_DIAG3, 128, KV2, 128, HD_64 | HD_96},
+    {8, DQ32_DIAG4, 128, KV2, 128, HD_64 | HD_96},
+    {32, DQ32_PIPE, 128, KV32, 128, HD_64 | HD_96},
+    {102, DQ16_NQ1, 64, KV2, 128, HD_64 | HD_96},
+    {116, DQ16_NQ1, 64, KV1, 64, HD_ALL},
+#endif
+};
+constexpr bool bwd_has(DqBuild b, int hdp) {
+    for (const BwdVariant& v : BWD_VARIANTS)
+        if (v.dq == b && (v.hds & hd_bit(hdp))) return true;
+    return false;
+}
+constexpr bool bwd_has(KvBuild b, int hdp) {
+    for (const BwdVariant& v : BWD_VARIANTS)
+        if (v.kv == b && (v.hds & hd_bit(hdp))) return true;
+    return false;
+}
+using BwdKernel = void (*)(AttnBwdP);
+template <int HD, bool C, DqBuild B>
+constexpr BwdKernel dq_kernel() {
+    if constexpr (B == DQ16_NQ2 || B == DQ16_NQ1) return k_attn_bwd_dq<HD, C, B == DQ16_NQ2 ? 2 : 1>;
+    else return dq32<HD, C, B>();
+}
+template <int HD, bool C, KvBuild B>
+constexpr BwdKernel kv_kernel() {
+    if constexpr (B == KV1) return k_attn_bwd_dkdv<HD, C>;
+    else if constexpr (B == KV2) return k_attn_bwd_dkdv2<HD, C>;
+#ifdef KD_AB_BUILD   // tools/ab/attention_bwd_dkdv32.inc
+    else return k_attn_bwd_dkdv32<HD, C>;
 #else
-    (void)grid; (void)smem; (void)st; (void)p;
+    else static_assert(B != KV32, "k_attn_bwd_dkdv32 is in the A/B library only");
 #endif
 }
 
-template <int HD, bool C>
-void launch_dkdv(bool kv16, dim3 grid, size_t smem, hipStream_t st, const AttnBwdP& p) {
-    if constexpr (HD == 128) {
-        grid.z = (p.S + 63) / 64;
-        hipLaunchKernelGGL((k_attn_bwd_dkdv<HD, C>), grid, dim3(256), smem, st, p);
-    } else {
-#ifdef KD_AB_BUILD
-        if (kv16) hipLaunchKernelGGL((k_attn_bwd_dkdv<HD, C>), grid, dim3(256), smem, st, p);
-        else
-#endif
-        hipLaunchKernelGGL((k_attn_bwd_dkdv2<HD, C>), grid, dim3(256), smem, st, p);
-        (void)kv16;
-    }
-}
+}  // namespace
 
-// dQ (+ delta) by the 32x32x16 k_attn_bwd_dq32 (head dims 64 / 96). A/B library: `diag` 1 = the
-// unpipelined build (hd 64: three workgroups per CU), 2-5 = its DIAG builds 1-4
-template <int HD, bool C>
-int launch_dq32(int diag, dim3 grid_q, size_t smem_q, hipStream_t st, const AttnBwdP& p) {
-    if constexpr (HD == 128) {
-        (void)diag; (void)grid_q; (void)smem_q; (void)st; (void)p;
-        return fail(KD_ERR_SHAPE, "attn_bwd: no 32x32 dQ kernel for head dim 128");
-    } else {
-#ifdef KD_AB_BUILD
-        if (diag == 1) hipLaunchKernelGGL((k_attn_bwd_dq32<HD, C, HD == 64 ? 3 : 2, 0, false>), grid_q, dim3(256), smem_q, st, p);
-        else if (diag == 2) hipLaunchKernelGGL((k_attn_bwd_dq32<HD, C, 2, 1>), grid_q, dim3(256), smem_q, st, p);
-        else if (diag == 3) hipLaunchKernelGGL((k_attn_bwd_dq32<HD, C, 2, 2>), grid_q, dim3(256), smem_q, st, p);
-        else if (diag == 4) hipLaunchKernelGGL((k_attn_bwd_dq32<HD, C, 2, 3>), grid_q, dim3(256), smem_q, st, p);
-        else if (diag == 5) hipLaunchKernelGGL((k_attn_bwd_dq32<HD, C, 2, 4>), grid_q, dim3(256), smem_q, st, p);
-        else
-#endif
-        hipLaunchKernelGGL((k_attn_bwd_dq32<HD, C>), grid_q, dim3(256), smem_q, st, p);
-        (void)diag;
-        KD_LAUNCH_CHECK("k_attn_bwd_dq32");
-        return KD_OK;
-    }
+int launch_attn_fwd(const kd_attn_desc* d, void* stream_) {
+    KD_CHECK_ARG(d && d->q && d->k && d->v && d->o, "attn_fwd: null pointer");
+    if (const int rc = check_attn_shape("attn_fwd", d->B, d->S, d->H, d->HKV, d->hd, d->hdp)) return rc;
+    static const bool nq1 = env_is_1("KD_ATTN_FWD_NQ");
+    const FwdVariant* v = variant_row(FWD_VARIANTS, env_code("KD_ATTN_FWD_V"), d->hdp);
+    KD_CHECK_ARG(v, "attn_fwd: KD_ATTN_FWD_V names no forward variant");
+    if (nq1 && v->build == F16_NQ2) v = variant_row(FWD_VARIANTS, v->code + 100, d->hdp);
+    AttnP p{(const bf16*)d->q, (const bf16*)d->k, (const bf16*)d->v, (bf16*)d->o, d->lse,
+            d->B, d->H, d->HKV, d->S, d->hd, (float)(1.4426950408889634 / std::sqrt((double)d->hd))};
+    hipStream_t st = as_stream(stream_);
+    const size_t smem = 2 * 2 * 64 * (d->hdp == 64 ? 128 : 256);   // [2][K TILE | V TILE]
+    const dim3 grid(d->H, d->B, (d->S + v->qrows - 1) / v->qrows);
+    return dispatch(d->hdp, d->causal, [&](auto hd_c, auto causal_c) {
+        constexpr int HD = decltype(hd_c)::value;
+        constexpr bool C = decltype(causal_c)::value;
+        for_each_build<N_FWD_BUILDS>([&](auto b_c) {
+            constexpr FwdBuild B = (FwdBuild)decltype(b_c)::value;
+            if constexpr (fwd_has(B, HD)) {
+                if (v->build == B) hipLaunchKernelGGL((fwd_kernel<HD, C, B>()), grid, dim3(v->block), smem, st, p);
+            }
+        });
+        KD_LAUNCH_CHECK("k_attn_fwd");
+        return (int)KD_OK;
+    });
 }
-
-// dQ by the 16x16x32 k_attn_bwd_dq: head dim 128 in the product (no 32x32 build there; the teacher
-// runs no backward in the step), every head dim in the A/B library (the round-6 pair, KD_ATTN_BWD_V=2)
-template <int HD, bool C>
-int launch_dq16(int nq, dim3 grid_q, size_t smem_q, hipStream_t st, const AttnBwdP& p) {
-#ifdef KD_AB_BUILD
-    constexpr bool avail = true;
-#else
-    constexpr bool avail = HD == 128;
-#endif
-    if constexpr (!avail) {
-        (void)nq; (void)grid_q; (void)smem_q; (void)st; (void)p;
-        return fail(KD_ERR_SHAPE, "attn_bwd: the 16x16 dQ kernel runs head dim 128 only (k_attn_bwd_dq32 below)");
-    } else {
-        if (nq == 2) hipLaunchKernelGGL((k_attn_bwd_dq<HD, C, 2>), grid_q, dim3(256), smem_q, st, p);
-        else launch_dq1<HD, C>(grid_q, smem_q, st, p);
-        KD_LAUNCH_CHECK("k_attn_bwd_dq");
-        return KD_OK;
-    }
-}
-
-#ifdef KD_AB_BUILD
-template <int HD, bool C>
-int launch_dkdv32(dim3 grid, size_t smem_kv, hipStream_t st, const AttnBwdP& p) {
-    if constexpr (HD == 128) {
-        (void)grid; (void)smem_kv; (void)st; (void)p;
-        return fail(KD_ERR_SHAPE, "attn_bwd: no 32x32 dK / dV kernel for head dim 128");
-    } else {
-        hipLaunchKernelGGL((k_attn_bwd_dkdv32<HD, C>), grid, dim3(256), smem_kv, st, p);
-        KD_LAUNCH_CHECK("k_attn_bwd_dkdv32");
-        return KD_OK;
-    }
-}
-#endif  // KD_AB_BUILD
 
 size_t attn_bwd_workspace_size(const kd_attn_bwd_desc* d) {
     if (!d || d->HKV <= 0 || d->H == d->HKV) return 0;
@@ -1901,72 +1951,46 @@ int launch_attn_bwd(const kd_attn_bwd_desc* d, void* stream_) {
                  "attn_bwd: RoPE tables only with dqkv, GQA (H > HKV) and hd == hdp, hd % 32 == 0");
     KD_CHECK_ARG(!d->dqkv || d->H == d->HKV || (d->hd % 8 == 0),
                  "attn_bwd: dqkv with GQA needs hd % 8 == 0");
-    KD_CHECK_SHAPE(d->B > 0 && d->S > 0 && d->HKV > 0 && d->H % d->HKV == 0 && d->hd % 4 == 0 && d->hd <= d->hdp,
-                   "attn_bwd: shape");
-    KD_CHECK_SHAPE(d->hdp == 64 || d->hdp == 96 || d->hdp == 128, "attn_bwd: padded head dim must be 64/96/128");
-    KD_CHECK_SHAPE(!(d->hdp == 96 && d->hd > 80) && !(d->hdp == 64 && d->hd > 64), "attn_bwd: hd exceeds tile cover");
+    if (const int rc = check_attn_shape("attn_bwd", d->B, d->S, d->H, d->HKV, d->hd, d->hdp)) return rc;
     KD_CHECK_SHAPE(d->hd % 8 == 0, "attn_bwd: hd must be a multiple of 8 (16-B dO rows)");
     const size_t need = attn_bwd_workspace_size(d);
     if (need && (!d->workspace || d->workspace_bytes < need))
         return fail(KD_ERR_WORKSPACE, "attn_bwd: GQA needs kd_attn_bwd_workspace_size() bytes of workspace");
+    static const bool nq1 = env_is_1("KD_ATTN_DQ_NQ");
+    const BwdVariant* v = variant_row(BWD_VARIANTS, env_code("KD_ATTN_BWD_V"), d->hdp);
+    KD_CHECK_ARG(v, "attn_bwd: KD_ATTN_BWD_V names no backward variant");
+    if (nq1 && v->dq == DQ16_NQ2) v = variant_row(BWD_VARIANTS, v->code + 100, d->hdp);
     hipStream_t st = as_stream(stream_);
-    // delta = rowsum(dO * O) is computed by the dQ kernel (its lanes hold the dO rows already) and
-    // written for the dK / dV kernel, which therefore runs second
     const double sc = 1.0 / std::sqrt((double)d->hd);
     float* dkp = need ? (float*)d->workspace : nullptr;
     float* dvp = need ? dkp + (size_t)d->B * d->H * d->S * d->hdp : nullptr;
     AttnBwdP p{(const bf16*)d->q, (const bf16*)d->k, (const bf16*)d->v, (const bf16*)d->dO, (const bf16*)d->o, d->lse, d->delta,
                d->dq, (bf16*)d->dk, (bf16*)d->dv, dkp, dvp, d->B, d->H, d->HKV, d->S, d->hd, (float)sc,
                (float)(sc * 1.4426950408889634), (bf16*)d->dqkv, d->ld_qkv, d->cos_t, d->sin_t};
-#ifdef KD_AB_BUILD
-    // head dims 64 / 96 (A/B; read per call): unset / 0 = the product pair (k_attn_bwd_dq32 +
-    // k_attn_bwd_dkdv2); 2 = the round-6 16x16x32 pair (k_attn_bwd_dq + k_attn_bwd_dkdv2); 16 = the
-    // one-sub-tile dK / dV kernel; 32 = k_attn_bwd_dq32 + k_attn_bwd_dkdv32; 3 / 5-8 = dq32 unpipelined
-    // (hd 64: three workgroups per CU) / its DIAG builds 1-4 (timing only). KD_ATTN_DQ_NQ=1: one query sub-tile per
-    // 16x16 dQ wave
-    const char* bve = std::getenv("KD_ATTN_BWD_V");
-    const int bv = bve ? std::atoi(bve) : 0;
-    const bool kv16 = bv == 16, dq32 = bv != 2 && bv != 16, kv32 = bv == 32;
-    const int diag = bv == 3 ? 1 : (bv >= 5 && bv <= 8 ? bv - 3 : 0);
-    static const int nq_dq = [] { const char* e = std::getenv("KD_ATTN_DQ_NQ"); return (e && e[0] == '1') ? 1 : 2; }();
-#else
-    constexpr bool kv16 = false, dq32 = true;
-    constexpr int diag = 0, nq_dq = 2;
-#endif
-    dim3 grid(d->H, d->B, kv16 ? (d->S + 63) / 64 : (d->S + 127) / 128);
-    const int qrows = dq32 ? 128 : 64 * nq_dq;   // query rows per dQ workgroup
-    dim3 grid_q(d->H, d->B, (d->S + qrows - 1) / qrows);
+    const dim3 grid_q(d->H, d->B, (d->S + v->qrows - 1) / v->qrows), grid_kv(d->H, d->B, (d->S + v->keys - 1) / v->keys);
     const int rb = d->hdp == 64 ? 128 : 256;
-    const size_t smem_kv = 2 * (2 * 64 * rb + 512);
-    const size_t smem_q = 2 * 2 * 64 * rb;
-#ifdef KD_AB_BUILD
-#define KD_AB_KV32(HD, C)                                                                     \
-    if (HD != 128 && kv32) {                                                                  \
-        const int rc = launch_dkdv32<HD, C>(grid, smem_kv, st, p);                            \
-        if (rc != KD_OK) return rc;                                                           \
-        break;                                                                                \
-    }
-#else
-#define KD_AB_KV32(HD, C)
-#endif
-#define LAUNCH(HD, C)                                                                         \
-    do {                                                                                      \
-        if (HD != 128 && dq32) {                                                              \
-            const int rc = launch_dq32<HD, C>(diag, grid_q, smem_q, st, p);                   \
-            if (rc != KD_OK) return rc;                                                       \
-        } else {                                                                              \
-            const int rc = launch_dq16<HD, C>(nq_dq, grid_q, smem_q, st, p);                  \
-            if (rc != KD_OK) return rc;                                                       \
-        }                                                                                     \
-        KD_AB_KV32(HD, C)                                                                     \
-        launch_dkdv<HD, C>(kv16, grid, smem_kv, st, p);                                       \
-        KD_LAUNCH_CHECK("k_attn_bwd_dkdv");                                                   \
-    } while (0)
-    if (d->hdp == 64) { if (d->causal) LAUNCH(64, true); else LAUNCH(64, false); }
-    else if (d->hdp == 96) { if (d->causal) LAUNCH(96, true); else LAUNCH(96, false); }
-    else { if (d->causal) LAUNCH(128, true); else LAUNCH(128, false); }
-#undef LAUNCH
-#undef KD_AB_KV32
+    const size_t smem_q = 2 * 2 * 64 * rb;           // [2][K TILE | V TILE]
+    const size_t smem_kv = 2 * (2 * 64 * rb + 512);   // [2][Q TILE | dO TILE | lse2 64 | delta 64]
+    const int rc = dispatch(d->hdp, d->causal, [&](auto hd_c, auto causal_c) {
+        constexpr int HD = decltype(hd_c)::value;
+        constexpr bool C = decltype(causal_c)::value;
+        for_each_build<N_DQ_BUILDS>([&](auto b_c) {
+            constexpr DqBuild B = (DqBuild)decltype(b_c)::value;
+            if constexpr (bwd_has(B, HD)) {
+                if (v->dq == B) hipLaunchKernelGGL((dq_kernel<HD, C, B>()), grid_q, dim3(256), smem_q, st, p);
+            }
+        });
+        KD_LAUNCH_CHECK(v->dq <= DQ32_PIPE ? "k_attn_bwd_dq32" : "k_attn_bwd_dq");
+        for_each_build<N_KV_BUILDS>([&](auto b_c) {
+            constexpr KvBuild B = (KvBuild)decltype(b_c)::value;
+            if constexpr (bwd_has(B, HD)) {
+                if (v->kv == B) hipLaunchKernelGGL((kv_kernel<HD, C, B>()), grid_kv, dim3(256), smem_kv, st, p);
+            }
+        });
+        KD_LAUNCH_CHECK(v->kv == KV32 ? "k_attn_bwd_dkdv32" : "k_attn_bwd_dkdv");
+        return (int)KD_OK;
+    });
+    if (rc != KD_OK) return rc;
     if (need) {
         const int dcols = 16 * (d->hdp == 64 ? 4 : (d->hdp == 96 ? 5 : 8));
         const int64_t work = (int64_t)d->B * d->HKV * d->S * dcols / 4;

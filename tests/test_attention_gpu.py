@@ -59,6 +59,10 @@ CASES = [  # B, H, HKV, S, hd, hdp, causal
     (1, 16, 16, 729, 72, 96, False),      # SigLIP, all heads
     (1, 28, 4, 1536, 128, 128, True),     # teacher at the step's full sequence length
     (1, 2, 2, 33, 128, 128, False),       # one partial 64-key tile, 33 of 128 query rows
+    # one small case per product instance that a mis-wired dispatch could swap and nothing above runs
+    (1, 2, 2, 129, 72, 96, True),         # hd 96 causal: two key blocks, one row into the second 128-row query block
+    (1, 4, 2, 65, 64, 64, False),         # hd 64 GQA without a mask: one row into the second 64-key tile, the group sum
+    (1, 2, 1, 1, 64, 64, True),           # S = 1
 ]
 
 

@@ -16,10 +16,10 @@ pytestmark = pytest.mark.gpu
 @pytest.mark.parametrize("variant", ["16", "32"])
 @pytest.mark.parametrize("B,H,HKV,S,hd,hdp,causal", [CASES[1], CASES[2], CASES[3], CASES[7], CASES[8]])
 def test_attn_fwd_variants_agree(B, H, HKV, S, hd, hdp, causal, variant, dev):
-    """The pipelined 32x32x16 kernel (default), the unpipelined one (KD_ATTN_FWD_V=32) and the
-    16x16x32 one (=16) compute the same softmax; they differ only in the fp32 summation order
-    of the scores / row sums and the sub-tile width of the lazy rescale (which changes the
-    bf16 rounding of P): outputs within 2^-7 (|o| + P|V|), lse within 1e-5 relative."""
+    """The 32x32x16 k_attn_fwd32 (default; KD_ATTN_FWD_V=32 names the same build, F32_DMA) and the
+    16x16x32 k_attn_fwd (=16) compute the same softmax; the two kernels differ only in the fp32
+    summation order of the scores / row sums and the sub-tile width of the lazy rescale (which
+    changes the bf16 rounding of P): outputs within 2^-7 (|o| + P|V|), lse within 1e-5 relative."""
     import os
     ops = _ops()
     q, k, v = _inputs(B, H, HKV, S, hd, hdp, dev)
@@ -98,3 +98,23 @@ def test_attn_fwd_two_blocks_per_wave_bitexact(B, H, HKV, S, hd, hdp, causal, de
         os.environ.pop("KD_ATTN_FWD_V", None)
     (o0, l0), (o1, l1) = outs
     assert torch.equal(o0, o1) and torch.equal(l0, l1)
+
+
+@pytest.mark.parametrize("env,code", [("KD_ATTN_FWD_V", "17"), ("KD_ATTN_FWD_V", "31"), ("KD_ATTN_BWD_V", "1"),
+                                      ("KD_ATTN_BWD_V", "4"), ("KD_ATTN_BWD_V", "33")])
+def test_unknown_variant_code_is_rejected(env, code, dev):
+    """A code in neither variant table is KD_ERR_ARG before any launch (it used to run the 16x16x32
+    forward, or the product backward pair, silently)."""
+    import os
+    ops = _ops()
+    q, k, v = _inputs(1, 2, 2, 65, 64, 64, dev)
+    o, lse = ops.attn_fwd(q, k, v, 64, True)
+    os.environ[env] = code
+    try:
+        with pytest.raises(RuntimeError, match=f"KD_ERR_ARG.*{env} names no"):
+            if env == "KD_ATTN_FWD_V":
+                ops.attn_fwd(q, k, v, 64, True)
+            else:
+                ops.attn_bwd(q, k, v, o, torch.ones_like(o), lse, 64, True)
+    finally:
+        os.environ.pop(env, None)

@@ -17,12 +17,12 @@ template <typename K> static void show(const char* name, K k, size_t smem) {
 int main() {
     using namespace kd;
     show("k_attn_fwd<128,true,2>", k_attn_fwd<128, true, 2>, 65536);
-    show("k_attn_fwd32<128,true,false>", k_attn_fwd32<128, true, false>, 65536);
-    show("k_attn_fwd32<128,false,false>", k_attn_fwd32<128, false, false>, 65536);
-    show("k_attn_fwd32<128,true,true>", k_attn_fwd32<128, true, true>, 65536);
-    show("k_attn_fwd32<64,true,false>", k_attn_fwd32<64, true, false>, 32768);
-    show("k_attn_fwd32<96,false,false>", k_attn_fwd32<96, false, false>, 65536);
-    show("k_attn_fwd32<128,true,false> 48K", k_attn_fwd32<128, true, false>, 49152);
+    show("fwd32<128,true,F32_DMA>", fwd32<128, true, F32_DMA>(), 65536);
+    show("fwd32<128,false,F32_DMA>", fwd32<128, false, F32_DMA>(), 65536);
+    show("fwd32<128,true,F32_REGSTAGE>", fwd32<128, true, F32_REGSTAGE>(), 65536);
+    show("fwd32<64,true,F32_DMA>", fwd32<64, true, F32_DMA>(), 32768);
+    show("fwd32<96,false,F32_DMA>", fwd32<96, false, F32_DMA>(), 65536);
+    show("fwd32<128,true,F32_DMA> 48K", fwd32<128, true, F32_DMA>(), 49152);
     int dev = 0; hipDeviceProp_t pr{};
     (void)hipGetDeviceProperties(&pr, dev);
     printf("sharedMemPerMultiprocessor %zu maxSharedMemoryPerMultiProcessor %zu sharedMemPerBlock %zu\n",
