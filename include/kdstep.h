@@ -724,6 +724,29 @@ int kd_kv_beam_reorder(void* k_cache, void* v_cache, int layers, int P, int K, i
                        const int32_t* parent, const int32_t* cur_dev, const int32_t* prompt_len, int tail_max,
                        void* stream);
 
+/* Log-probabilities of given columns (score_answers(): candidate answers under teacher forcing).
+ * One workgroup per row r of `rows` (1 <= rows <= 2^20) rows of N bf16 scores (1 <= N <= 262144),
+ * row r at scores + r * ld_scores; ld_scores >= N, or 0: every row reads the same N scores (many
+ * targets on one logits row).  A row need not be 16-byte aligned (odd ld_scores).  target: device
+ * int32 [rows], the column t that row r is scored at.  With s'_i the score as fp32, a NaN read as
+ * -inf, and mx the largest s':
+ *   lse: kd_gen_beam_topk's value, bit for bit (the maximum, then the integer sum of
+ *     floor(exp(s - mx) * 2^40) over the scores that are not NaN; lse = mx + (float)(log Z - 40 ln 2));
+ *     a row with nothing above -inf is dead;
+ *   logprob[r] = s_t - lse (fp32, correctly rounded); -inf, never NaN, where s_t is NaN or -inf, the
+ *     row is dead, or t lies outside [0, N);
+ *   rank[r] (optional, int32) = #{ i : s'_i > s'_t, or s'_i == s'_t and i < t }, N for t outside
+ *     [0, N): 0 where t is what the greedy select takes from the unprocessed row;
+ *   top1[r] (optional, int32) = the lowest i with s'_i == mx, 0 for a dead row;
+ *   top1_logprob[r] (optional, fp32) = mx - lse, -inf for a dead row.
+ * rank and top1 share one further pass over the row, skipped where both are NULL.  A +inf score gives
+ * an unspecified result, as in kd_gen_beam_topk.  No workspace, no floating-point atomics, no host
+ * sync: stream-ordered, bit-deterministic, and a row's outputs do not depend on the other rows.
+ * Null scores / target / logprob -> KD_ERR_ARG; N, rows or ld_scores out of range -> KD_ERR_SHAPE;
+ * both before any device work. */
+int kd_score_rows(const void* scores, int64_t ld_scores, int N, int rows, const int32_t* target, float* logprob,
+                  int32_t* rank, int32_t* top1, float* top1_logprob, void* stream);
+
 /* --------------------------------------------------------- model runtime ---- */
 /* One LLaVA-OneVision instance (SigLIP -> projector -> anyres pack -> Qwen2 -> lm_head)
  * whose forward and backward layer loops run in the library (SURVEY §8b "teacher forward"

@@ -242,6 +242,10 @@ int kd_kv_beam_reorder(void* kc, void* vc, int layers, int P, int K, int HKV, in
                        const int32_t* cur, const int32_t* prompt_len, int tail_max, void* s) {
     return kd::launch_kv_beam_reorder(kc, vc, layers, P, K, HKV, smax, hd, parent, cur, prompt_len, tail_max, s);
 }
+int kd_score_rows(const void* scores, int64_t lds, int N, int rows, const int32_t* target, float* logprob, int32_t* rank,
+                  int32_t* top1, float* top1_logprob, void* s) {
+    return kd::launch_score_rows(scores, lds, N, rows, target, logprob, rank, top1, top1_logprob, s);
+}
 size_t kd_image_resize_workspace_size(int H, int W, int oh, int ow) { return kd::image_resize_ws(H, W, oh, ow); }
 int kd_image_resize_u8(const uint8_t* in, int H, int W, uint8_t* out, int oh, int ow, void* ws, size_t ws_bytes,
                        void* s) {

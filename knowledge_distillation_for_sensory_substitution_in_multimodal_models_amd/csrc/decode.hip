@@ -1547,6 +1547,38 @@ __device__ __forceinline__ void bt_for_each(const bf16* __restrict__ scores, con
     for (int i = (v8 << 3) + threadIdx.x; i < N; i += nt) f(i, (float)scores[i], FLAGS ? (uint32_t)flags[i] : 0u);
 }
 
+// A row's logsumexp over every logit that is not NaN, the one copy k_gen_beam_topk and k_score_rows
+// share: mx = the largest such logit, Z = the integer sum of floor(exp(s - mx) * 2^40) (the maximum
+// itself weighs 2^40), the same in every thread whatever order the waves ran in.  dead: nothing above
+// -inf (lse is then 0 and means nothing).  1024 threads; red and wsum: 16 LDS words each.  flags only
+// decides, with the row's own alignment, where bt_for_each takes its 16-byte loads.
+struct BtLse {
+    float mx, lse;
+    bool dead;
+};
+__device__ __forceinline__ BtLse bt_row_lse(const bf16* __restrict__ logits, const uint8_t* __restrict__ flags, int V,
+                                            float* red, u64* wsum) {
+    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+    float mx = -INFINITY;
+    bt_for_each<false>(logits, flags, V, [&](int, float s, uint32_t) { mx = fmaxf(mx, s); });   // fmaxf drops a NaN
+    mx = block_max<16>(mx, red);
+    const bool dead = !(mx > -INFINITY);
+    u64 z = 0;
+    if (!dead)
+        bt_for_each<false>(logits, flags, V, [&](int, float s, uint32_t) {
+            if (s == s) z += (u64)((s == mx ? 1.0f : expf(s - mx)) * 1099511627776.0f);
+        });
+    z = gs_wave_sum(z);
+    if (lane == 0) wsum[wv] = z;
+    __syncthreads();
+    z = 0;
+#pragma unroll
+    for (int i = 0; i < 16; ++i) z += wsum[i];
+    // Z >= 2^40 (the maximum weighs 1): log in double, one rounding to fp32, one more for the sum
+    const float lse = dead ? 0.f : __fadd_rn(mx, (float)(log((double)z) - 40.0 * 0.69314718055994530942));
+    return {mx, lse, dead};
+}
+
 // Row b = blockIdx.x: acc_i = processed(logit_i - lse) + run_score[b] over the full vocabulary, and
 // its M largest (acc, token) pairs, descending, the lower token first among equals.  lse is order
 // free: the row maximum, then the integer sum of floor(exp(s - max) * 2^40) (k_gen_sample's fixed
@@ -1588,24 +1620,9 @@ __global__ void __launch_bounds__(1024) k_gen_beam_topk(const bf16* __restrict__
         __syncthreads();
     }
 
-    // ---- the row's logsumexp over every logit that is not NaN
-    float mx = -INFINITY;
-    bt_for_each<false>(logits, flags, V, [&](int, float s, uint32_t) { mx = fmaxf(mx, s); });   // fmaxf drops a NaN
-    mx = block_max<16>(mx, red);
-    const bool dead = !(mx > -INFINITY);   // nothing above -inf: every entry is (-inf, 0)
-    u64 z = 0;
-    if (!dead)
-        bt_for_each<false>(logits, flags, V, [&](int, float s, uint32_t) {
-            if (s == s) z += (u64)((s == mx ? 1.0f : expf(s - mx)) * 1099511627776.0f);
-        });
-    z = gs_wave_sum(z);
-    if (lane == 0) wsum[wv] = z;
-    __syncthreads();
-    z = 0;
-#pragma unroll
-    for (int i = 0; i < 16; ++i) z += wsum[i];
-    // Z >= 2^40 (the maximum weighs 1): log in double, one rounding to fp32, one more for the sum
-    const float lse = dead ? 0.f : __fadd_rn(mx, (float)(log((double)z) - 40.0 * 0.69314718055994530942));
+    const BtLse rl = bt_row_lse(logits, flags, V, red, wsum);
+    const bool dead = rl.dead;   // every entry is (-inf, 0)
+    const float lse = rl.lse;
 
     // ---- acc into the workspace, and the histogram of the keys' top byte
     const float rs = run_score[b];
@@ -1684,6 +1701,64 @@ __global__ void __launch_bounds__(1024) k_gen_beam_topk(const bf16* __restrict__
         }
         cand_score[(size_t)b * M + rank] = si;
         cand_tok[(size_t)b * M + rank] = ti;
+    }
+}
+
+// Row r = blockIdx.x (include/kdstep.h, kd_score_rows): the log-probability of column t = target[r]
+// under the row's softmax, k_gen_beam_topk's lse (bt_row_lse) without its M-best search.  With s' the
+// score as fp32 and a NaN read as -inf: rank = the entries that the greedy select takes before t
+// (s' larger, or equal at a lower column), top1 = the lowest column at the maximum.  Both are integer
+// reductions (a count, a minimum), so nothing depends on the order the waves ran in.  They share the
+// third pass over the row, which is skipped where neither is asked for.  lds = 0: every row reads the
+// same N scores.
+__global__ void __launch_bounds__(1024) k_score_rows(const bf16* __restrict__ scores_all, int64_t lds, int N,
+                                                     const int* __restrict__ target, float* __restrict__ logprob,
+                                                     int* __restrict__ rank, int* __restrict__ top1,
+                                                     float* __restrict__ top1_logprob) {
+    __shared__ u64 wsum[16];
+    __shared__ float red[16];
+    __shared__ int wcnt[16];
+    __shared__ int wmin[16];
+    const int r = blockIdx.x, lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+    const bf16* scores = scores_all + (size_t)r * lds;
+    const int t = target[r];
+    const bool inside = t >= 0 && t < N;
+    const BtLse rl = bt_row_lse(scores, (const uint8_t*)nullptr, N, red, wsum);
+    float st = inside ? (float)scores[t] : -INFINITY;
+    if (!(st == st)) st = -INFINITY;
+    if (threadIdx.x == 0) {
+        logprob[r] = (rl.dead || !(st > -INFINITY)) ? -INFINITY : __fsub_rn(st, rl.lse);
+        if (top1_logprob) top1_logprob[r] = rl.dead ? -INFINITY : __fsub_rn(rl.mx, rl.lse);
+    }
+    if (!rank && !top1) return;
+
+    int cnt = 0, first = N;
+    const float mx = rl.mx;
+    bt_for_each<false>(scores, (const uint8_t*)nullptr, N, [&](int i, float s, uint32_t) {
+        if (!(s == s)) s = -INFINITY;
+        cnt += (s > st || (s == st && i < t)) ? 1 : 0;
+        if (s == mx) first = min(first, i);
+    });
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+        cnt += __shfl_xor(cnt, o, 64);
+        first = min(first, __shfl_xor(first, o, 64));
+    }
+    if (lane == 0) {
+        wcnt[wv] = cnt;
+        wmin[wv] = first;
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        cnt = 0;
+        first = N;
+#pragma unroll
+        for (int w = 0; w < 16; ++w) {
+            cnt += wcnt[w];
+            first = min(first, wmin[w]);
+        }
+        if (rank) rank[r] = inside ? cnt : N;
+        if (top1) top1[r] = rl.dead ? 0 : first;
     }
 }
 
@@ -2288,6 +2363,17 @@ int launch_gen_beam_topk(const void* logits, int64_t ldl, int V, const int* ids,
                        const_cast<int64_t*>(seq), smax, cur_dev, run_score, penalty, ngram, M, (unsigned char*)ws,
                        cand_score, cand_tok);
     KD_LAUNCH_CHECK("k_gen_beam_topk");
+    return KD_OK;
+}
+
+int launch_score_rows(const void* scores, int64_t lds, int N, int rows, const int* target, float* logprob, int* rank,
+                      int* top1, float* top1_logprob, void* stream) {
+    KD_CHECK_ARG(scores && target && logprob, "score_rows: null pointer");
+    KD_CHECK_SHAPE(N >= 1 && N <= GS_N_MAX && rows >= 1 && rows <= (1 << 20) && (lds == 0 || lds >= N),
+                   "score_rows: 1 <= N <= 262144, 1 <= rows <= 2^20, ld_scores >= N or 0 (one shared row)");
+    hipLaunchKernelGGL(k_score_rows, dim3(rows), dim3(1024), 0, as_stream(stream), (const bf16*)scores, lds, N, target,
+                       logprob, rank, top1, top1_logprob);
+    KD_LAUNCH_CHECK("k_score_rows");
     return KD_OK;
 }
 

@@ -114,6 +114,8 @@ size_t gen_beam_topk_ws(int nb, int V);
 int launch_gen_beam_topk(const void* logits, int64_t ldl, int V, const int* ids, int A, const int64_t* seq, int smax,
                          int nb, const int* cur_dev, const float* run_score, float penalty, int ngram, int M, void* ws,
                          size_t ws_bytes, float* cand_score, int* cand_tok, void* stream);
+int launch_score_rows(const void* scores, int64_t lds, int N, int rows, const int* target, float* logprob, int* rank,
+                      int* top1, float* top1_logprob, void* stream);
 int launch_gen_beam_step(const float* cand_score, const int* cand_tok, int M, int K, int P, int64_t* seq, int smax,
                          int* cur_dev, float* run_score, int64_t* out, int* parent, int64_t* fin_seq, float* fin_score,
                          int* fin_len, int* open, int* live, const float* den, int max_new, const int64_t* eos_ids_host,

@@ -943,6 +943,37 @@ def generate_grouped(model, groups, max_new_tokens: int = 32, repetition_penalty
     return (outs, logs) if return_logits else outs
 
 
+def _extend_rows(model, layers: _Layers, kc, vc, toks, lens, bases):
+    """Ragged rows behind cached prefixes, through every layer at once (generate_grouped(): the questions behind an
+    image; score_answers(): the answers behind a prompt).  Slot b of the caches kc, vc [layers, nb, HKV, smax, hd]
+    holds bases[b] positions; its lens[b] tokens (toks: int64 on the device, slot after slot, at most
+    KD_GEMV_ROWS_MAX) sit at positions bases[b] + j, see the prefix and their own slot's rows up to themselves, and
+    leave their k/v in the cache -> (x [R, hidden] behind the last layer, row_start [nb + 1] int32)."""
+    T, dev = model.cfg.text, model.device
+    nq, nkv, hd = T.heads, T.kv_heads, T.head_dim
+    starts = [0]
+    for n in lens:
+        starts.append(starts[-1] + n)
+    R = starts[-1]
+    row_start = torch.tensor(starts, dtype=torch.int32, device=dev)
+    base = torch.tensor(list(bases), dtype=torch.int32, device=dev)
+    cur_rows = torch.tensor([P + j + 1 for P, n in zip(bases, lens) for j in range(n)],
+                            dtype=torch.int32, device=dev)   # position + 1, as the decode step's counter
+    src = torch.full((R,), -2, dtype=torch.int32, device=dev)   # token embedding (kd_embed_assemble)
+    cos, sin = model._rope_for(kc.shape[3])
+    cos_rows = torch.empty((R, cos.shape[1]), dtype=torch.float32, device=dev)
+    sin_rows = torch.empty_like(cos_rows)
+    ops.rope_rows(cos, sin, cur_rows, cos_rows, sin_rows)
+    table = model.P["language_model.model.embed_tokens.weight"]
+
+    def attend(i, qkv):
+        q, k, v = ops.qkv_split(qkv, 1, R, nq, nkv, hd, hd, cos_rows, sin_rows)   # row r rotated by its position
+        return ops.attn_extend(q[0], k[0], v[0], kc[i], vc[i], row_start, base, hd)
+
+    x = _layer_pass(ops.embed_assemble(toks, src, table, None, None, model.err), layers, ops.gemv_rows, attend)
+    return x, row_start
+
+
 def _generate_grouped_rows(model, chunk, carry, run: _Run):
     T = model.cfg.text
     dev = model.device
@@ -950,7 +981,7 @@ def _generate_grouped_rows(model, chunk, carry, run: _Run):
     Ls = [int(ids.shape[1]) for _, _, _, ids, _ in chunk]
     P0s = [P0 for *_, P0 in chunk]
     smax = max(Ls) + run.max_new_tokens
-    nq, nkv, hd = T.heads, T.kv_heads, T.head_dim
+    nkv, hd = T.kv_heads, T.head_dim
 
     kc = torch.empty((T.layers, nb, nkv, smax, hd), dtype=torch.bfloat16, device=dev)
     vc = torch.empty_like(kc)
@@ -968,8 +999,6 @@ def _generate_grouped_rows(model, chunk, carry, run: _Run):
 
     # ---- extend pass: every suffix row of the chunk through the layers at once (sub-ranges of
     # questions only if the rows exceed the kernels' cap; a question's bits do not depend on the split)
-    cos, sin = model._rope_for(smax)
-    table = model.P["language_model.model.embed_tokens.weight"]
     layers = _decode_layers(model)
     last = []
     b0 = 0
@@ -978,24 +1007,9 @@ def _generate_grouped_rows(model, chunk, carry, run: _Run):
         while b1 < nb and R + Ls[b1] - P0s[b1] <= KD_GEMV_ROWS_MAX:
             R += Ls[b1] - P0s[b1]
             b1 += 1
-        starts = [0]
-        for b in range(b0, b1):
-            starts.append(starts[-1] + Ls[b] - P0s[b])
-        row_start = torch.tensor(starts, dtype=torch.int32, device=dev)
-        base = torch.tensor(P0s[b0:b1], dtype=torch.int32, device=dev)
-        cur_rows = torch.tensor([P0s[b] + j + 1 for b in range(b0, b1) for j in range(Ls[b] - P0s[b])],
-                                dtype=torch.int32, device=dev)   # position + 1, as the decode step's counter
         toks = torch.cat([chunk[b][3][0, P0s[b]:] for b in range(b0, b1)]).contiguous()
-        src = torch.full((R,), -2, dtype=torch.int32, device=dev)   # token embedding (kd_embed_assemble)
-        cos_rows = torch.empty((R, cos.shape[1]), dtype=torch.float32, device=dev)
-        sin_rows = torch.empty_like(cos_rows)
-        ops.rope_rows(cos, sin, cur_rows, cos_rows, sin_rows)
-
-        def attend(i, qkv):
-            q, k, v = ops.qkv_split(qkv, 1, R, nq, nkv, hd, hd, cos_rows, sin_rows)   # row r rotated by its position
-            return ops.attn_extend(q[0], k[0], v[0], kc[i, b0:b1], vc[i, b0:b1], row_start, base, hd)
-
-        x = _layer_pass(ops.embed_assemble(toks, src, table, None, None, model.err), layers, ops.gemv_rows, attend)
+        x, row_start = _extend_rows(model, layers, kc[:, b0:b1], vc[:, b0:b1], toks,
+                                    [Ls[b] - P0s[b] for b in range(b0, b1)], P0s[b0:b1])
         last.append(x.index_select(0, (row_start[1:] - 1).long()))   # each question's last suffix row
         b0 = b1
     xl = last[0] if len(last) == 1 else torch.cat(last)

@@ -1140,3 +1140,33 @@ def kv_beam_reorder(k_cache: torch.Tensor, v_cache: torch.Tensor, K: int, parent
         raise RuntimeError("kv_beam_reorder: caches [layers, P * K, HKV, smax, hd] of one shape")
     NV.call("kd_kv_beam_reorder", k_cache.data_ptr(), v_cache.data_ptr(), layers, P, K, HKV, smax, hd, parent.data_ptr(),
             cur.data_ptr(), prompt_len.data_ptr(), int(tail_max), _stream())
+
+
+# ------------------------------------------------------------------------- scoring ----
+def score_rows(scores: torch.Tensor, target: torch.Tensor, *, rank: bool = True, top1: bool = True):
+    """The log-probability of column target[r] under row r's softmax (kd_score_rows, gen_beam_topk()'s
+    logsumexp bit for bit): scores [rows, N] bf16 with a contiguous last dim (any row stride >= N), or
+    [1, N] for target [rows]: every target is scored on the one row; target [rows] int32.
+    -> (logprob [rows] fp32, rank [rows] int32 or None, top1 [rows] int32 or None, top1_logprob [rows]
+    fp32 or None): rank = the columns the greedy select takes before the target, top1 = the lowest
+    column at the row's maximum.  A NaN counts as -inf; a target at -inf, outside [0, N) or in a row
+    with nothing above -inf scores -inf (rank N outside [0, N))."""
+    _require(scores, torch.bfloat16, "score_rows.scores")
+    _require(target, torch.int32, "score_rows.target")
+    if scores.dim() != 2 or scores.stride(1) != 1:
+        raise RuntimeError("score_rows: scores must be [rows, N] with a contiguous last dim")
+    if target.dim() != 1 or not target.is_contiguous() or target.numel() < 1:
+        raise RuntimeError("score_rows: target must be a contiguous, non-empty [rows] tensor")
+    R, N = scores.shape
+    rows = target.numel()
+    if R != rows and R != 1:
+        raise RuntimeError("score_rows: scores must hold one row per target, or one row for all of them")
+    ld = 0 if R != rows else (scores.stride(0) if rows > 1 else N)
+    dev = scores.device
+    logprob = torch.empty(rows, dtype=torch.float32, device=dev)
+    rank_t = torch.empty(rows, dtype=torch.int32, device=dev) if rank else None
+    top1_t = torch.empty(rows, dtype=torch.int32, device=dev) if top1 else None
+    top1_lp = torch.empty(rows, dtype=torch.float32, device=dev) if top1 else None
+    NV.call("kd_score_rows", scores.data_ptr(), ld, N, rows, target.data_ptr(), logprob.data_ptr(), _ptr(rank_t),
+            _ptr(top1_t), _ptr(top1_lp), _stream())
+    return logprob, rank_t, top1_t, top1_lp

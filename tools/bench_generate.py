@@ -46,7 +46,14 @@ prefill of one 336x336 prompt (L = 1536) + 32 greedy decode steps with the KV ca
                                                  calls: the baseline to interleave with).  --beams-only skips every
                                                  other leg; --beams-profile runs one greedy and one K-beam 32-token
                                                  generate_batch() eagerly and nothing else: the run to put under a
-                                                 kernel trace"""
+                                                 kernel trace
+    python tools/bench_generate.py --score 1,8,64   score_answers(): 16 prompts x C candidates of 3 tokens each, against
+                                                 generate_batch(max_new_tokens=1) on the same prompts (the sixteen
+                                                 prefills every such call pays: the floor, not a pass mark), and
+                                                 kd_score_rows alone on the shapes the call launches it at.
+                                                 --score-only skips every other leg; --score-profile C runs two
+                                                 score_answers() calls at C candidates and nothing else: the run to
+                                                 put under a kernel trace"""
 import argparse
 import inspect
 import sys
@@ -79,8 +86,13 @@ ap.add_argument("--beams", type=int, default=0, metavar="K", help="time generate
 ap.add_argument("--beams-only", action="store_true", help="only the --beams leg")
 ap.add_argument("--beams-profile", action="store_true",
                 help="one eager greedy and one K-beam generate_batch() of 16 // K prompts, nothing else")
+ap.add_argument("--score", default="", metavar="C[,C...]",
+                help="time score_answers() on 16 prompts x C candidates of 3 tokens against the sixteen prefills")
+ap.add_argument("--score-only", action="store_true", help="only the --score leg")
+ap.add_argument("--score-profile", type=int, default=0, metavar="C",
+                help="two score_answers() calls on 16 prompts x C candidates of 3 tokens, nothing else")
 args = ap.parse_args()
-if args.allowed_only or args.sample_only or args.beams_only:
+if args.allowed_only or args.sample_only or args.beams_only or args.score_only:
     args.answer_only, args.answer_tokens = True, 0
 SAMPLE = dict(do_sample=True, temperature=0.7, top_k=50, top_p=0.9, seed=20260101)
 
@@ -184,6 +196,66 @@ def beams_leg(K):
 
 if args.beams_only:
     beams_leg(max(2, args.beams))
+    sys.exit(0)
+
+
+def score_leg(Cs):
+    """16 prompts, C candidates of 3 tokens each: one prefill per prompt, 2 * C extend rows per prompt in chunks of 16
+    slots, 16 + ceil(16 * C / 16) kd_score_rows launches."""
+    rows = [synthetic_batch(1, dev, L=1536, seed=s) for s in range(16)]
+    ps = [(r["depth_input_ids"], r["depth_pixel_values"], r["image_sizes"]) for r in rows]
+    floor = [best_of(lambda: generate_batch(model, ps, max_new_tokens=1, **kw)) * 1e3 for _ in range(3)]
+    print("generate_batch, 16 prompts, max_new_tokens=1 (sixteen prefills), best of 3, three times: " +
+          " ".join(f"{t:.2f}" for t in floor) + f" ms (spread {(max(floor) / min(floor) - 1) * 100:.2f} %)")
+    try:
+        from knowledge_distillation_for_sensory_substitution_in_multimodal_models_amd import ops
+        from knowledge_distillation_for_sensory_substitution_in_multimodal_models_amd.data import TEXT_VOCAB
+        from knowledge_distillation_for_sensory_substitution_in_multimodal_models_amd.scoring import score_answers
+    except ImportError:
+        print("  this tree has no score_answers: its prefills only (the baseline to interleave with)")
+        return
+    for C in Cs:
+        g = torch.Generator().manual_seed(C)
+        answers = [[torch.randint(0, TEXT_VOCAB, (3,), generator=g).tolist() for _ in range(C)] for _ in ps]
+        st = {}
+        t = [best_of(lambda: score_answers(model, ps, answers, stats=st)) * 1e3 for _ in range(3)]
+        print(f"  score_answers, 16 prompts x {C:2d} candidates of 3 tokens, best of 3, three times: " +
+              " ".join(f"{x:.2f}" for x in t) + f" ms ({min(t) - min(floor):+.2f} ms on the prefills, "
+              f"{(min(t) - min(floor)) / (16 * C) * 1e3:.1f} us per candidate); {st}")
+
+    def launch(n_rows, n_targets, **k):   # kd_score_rows alone: device events around 50 launches
+        x = torch.randn(n_rows, STUDENT_05B.text.vocab, device=dev).bfloat16()
+        tg = torch.randint(0, STUDENT_05B.text.vocab, (n_targets,), device=dev, dtype=torch.int32)
+        ops.score_rows(x, tg, **k)
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        for _ in range(50):
+            ops.score_rows(x, tg, **k)
+        e1.record()
+        torch.cuda.synchronize()
+        return e0.elapsed_time(e1) / 50 * 1e3
+    for n_rows, n_targets in ((1, 1), (1, 8), (1, 64), (2, 2), (32, 32), (256, 256), (1024, 1024)):
+        print(f"  kd_score_rows, V = {STUDENT_05B.text.vocab}, {n_targets:4d} targets on {n_rows:4d} row(s): "
+              f"{launch(n_rows, n_targets):8.1f} us per launch; rank and top1 off: "
+              f"{launch(n_rows, n_targets, rank=False, top1=False):8.1f} us (50 back-to-back launches, host enqueue included)")
+
+
+if args.score_profile > 0:
+    from knowledge_distillation_for_sensory_substitution_in_multimodal_models_amd.data import TEXT_VOCAB  # noqa
+    from knowledge_distillation_for_sensory_substitution_in_multimodal_models_amd.scoring import score_answers  # noqa
+    rows = [synthetic_batch(1, dev, L=1536, seed=s) for s in range(16)]
+    prompts = [(r["depth_input_ids"], r["depth_pixel_values"], r["image_sizes"]) for r in rows]
+    g = torch.Generator().manual_seed(args.score_profile)
+    answers = [[torch.randint(0, TEXT_VOCAB, (3,), generator=g).tolist() for _ in range(args.score_profile)] for _ in prompts]
+    for _ in range(2):
+        st = {}
+        score_answers(model, prompts, answers, stats=st)
+    torch.cuda.synchronize()
+    print(f"two score_answers() calls, 16 prompts x {args.score_profile} candidates of 3 tokens: per call {st}")
+    sys.exit(0)
+
+if args.score_only:
+    score_leg([int(c) for c in args.score.split(",") if c] or [1, 8, 64])
     sys.exit(0)
 
 t32, t96 = timed(32), timed(96)
@@ -379,3 +451,6 @@ if args.sample or args.sample_only:
 
 if args.beams > 0:
     beams_leg(max(2, args.beams))
+
+if args.score:
+    score_leg([int(c) for c in args.score.split(",") if c])
