@@ -76,18 +76,44 @@ int kd_device_is_gfx950(int device);      /* 1 if device `device` is gfx950, els
  *  KD_LOSS_NONE         no teacher term (student CE only; BD SFT step, BD:90-109).
  * The student CE is the in-model causal-LM loss (shift by one, ignore -100, mean over
  * valid labels), HF ForCausalLMLoss; the teacher CE (computed and discarded by the
- * reference at DT:228) is reported as a side output when teacher logits are given. */
+ * reference at DT:228) is reported as a side output when teacher logits are given.
+ *
+ * Token-level divergences (not in the reference; new enum values, no ABI bump).  For every row
+ * (one (b, l) position), in fp32 from the bf16 logits, p = softmax(t[:V_s] / T), q = softmax(s / T):
+ *  KD_LOSS_FKL   D = sum_v p (log p - log q)                        forward KL
+ *  KD_LOSS_RKL   D = sum_v q (log q - log p)                        reverse KL (MiniLLM)
+ *  KD_LOSS_JSD   D = beta sum_v p (log p - log m) + (1 - beta) sum_v q (log q - log m),
+ *                m = beta p + (1 - beta) q, 0 < beta < 1 the weight on the teacher (GKD; TRL's
+ *                generalized_jsd_loss); beta is passed in `alpha`.
+ * KD term loss_out[0] = T^2 / R * sum over the row set of D: a sum over the vocabulary and a mean
+ * over rows, not the reference's mean over B*L*V.  Row set: every row (R = B*L), or with
+ * KD_LOSS_ROWS_TARGETS OR-ed into `variant` the rows whose shifted label is a CE target (R = n_valid,
+ * counted on the device; R = 0 gives a KD term and KD gradients of 0).  Rows outside the set get no
+ * KD gradient.  KD_LOSS_ROWS_TARGETS with variants 0-3 is KD_ERR_ARG, as is JSD's beta outside (0, 1).
+ * Gradient w.r.t. the student logits, with c = kd_weight * grad_scale * T / R:
+ *  FKL  c (q_j - p_j)
+ *  RKL  c q_j ((log q_j - log p_j) - D_row)
+ *  JSD  c (1 - beta) q_j (log(q_j / m_j) - K_row),  K_row = sum_v q log(q / m)
+ * (With KD_LOSS_ROWS_TARGETS and a CE coefficient of 0, the scale written to *dscale is c R: the
+ * host does not know n_valid.)
+ * log p and log q come from the logits and the row normalisers (never the log of an underflowed
+ * probability); an element whose p, q or m underflows in fp32 adds nothing (0 log 0 = 0). */
 typedef enum {
     KD_LOSS_NONE = 0,
     KD_LOSS_LOCA = 1,
     KD_LOSS_KL = 2,
-    KD_LOSS_KL_LOGTARGET = 3
+    KD_LOSS_KL_LOGTARGET = 3,
+    KD_LOSS_FKL = 4,
+    KD_LOSS_RKL = 5,
+    KD_LOSS_JSD = 6
 } kd_loss_variant;
+#define KD_LOSS_ROWS_TARGETS 0x100   /* flag OR-ed into kd_loss_params.variant (FKL / RKL / JSD) */
 
 typedef struct {
-    int32_t variant;        /* kd_loss_variant                                         */
+    int32_t variant;        /* kd_loss_variant (| KD_LOSS_ROWS_TARGETS)                 */
     float temperature;      /* T (self.T: DT 0.8, LB 1.0, FB 0.8)                       */
-    float alpha;            /* LoCa alpha (compute_loca_loss default 0.8)               */
+    float alpha;            /* LoCa alpha (compute_loca_loss default 0.8); for KD_LOSS_JSD the
+                               mixture weight beta                                       */
     float kd_weight;        /* weight of the (T^2-scaled) KD term in the total          */
     float ce_weight;        /* weight of the student CE in the total                    */
     float grad_scale;       /* dlogits multiplier (upstream dL/dtotal, e.g. 1/accum)    */

@@ -25,6 +25,8 @@ STATUS_NAMES = {
 
 # kd_loss_variant
 KD_LOSS_NONE, KD_LOSS_LOCA, KD_LOSS_KL, KD_LOSS_KL_LOGTARGET = 0, 1, 2, 3
+KD_LOSS_FKL, KD_LOSS_RKL, KD_LOSS_JSD = 4, 5, 6
+KD_LOSS_ROWS_TARGETS = 0x100   # flag OR-ed into KdLossParams.variant (FKL / RKL / JSD)
 
 
 class KdLossParams(C.Structure):

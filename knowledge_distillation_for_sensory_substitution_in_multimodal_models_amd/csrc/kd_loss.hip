@@ -20,6 +20,8 @@
 //   k_loss_grad : pass A sums the KD term and the row scalar S, pass B writes
 //                 dlogits; one 1024-thread workgroup per CU (256 rows in flight), so
 //                 pass B's re-read of the row is served by the Infinity Cache.
+//   k_loss_grad_div : the same two passes for the token-level divergences (forward KL, reverse KL,
+//                 JSD(beta)), which are not the reference's: mean over rows or over the CE's target rows.
 //   k_finalize  : deterministic fp64 reduction of the per-row partials.
 #include "common.h"
 
@@ -1146,6 +1148,159 @@ k_loss_grad(const bf16* __restrict__ T_, int64_t ld_t, const bf16* __restrict__ 
                             mask_g, kd_coef, ce_coef, D_, ld_d, part_kl, smask, red);
 }
 
+// Token-level divergences (KD_LOSS_FKL / RKL / JSD): per row D = sum over the vocabulary, the KD term
+// the mean of D over the row set (every row, or the CE's target rows: KD_LOSS_ROWS_TARGETS).  Built
+// like the two-read LoCa path above: base-2 log space with per-row constants,
+//   lp = (t - mp) a - cp = log2 p,   lq = (s - mq) a - cq = log2 q,   a = log2(e) / T,   p = 2^lp,  q = 2^lq
+// (mp, mq the row maxima, cp, cq = log2 of the sums), so log p and log q are never the log of an
+// underflowed probability, and an element whose p (q) underflowed multiplies a finite difference by 0.
+// The maximum is subtracted first (not folded into the constant as in k_loss_grad_loca): the rounding
+// error of lp is then relative to lp itself, and the probability of a row's dominant column is exact
+// to 2^-24 where a folded constant leaves 2^-24 |t a| -- on a saturated row (logits +-96) that error,
+// times a log ratio of 350, was a reverse-KL gradient of 3.5e-3 c where the true one is 0.  JSD needs log2 m of m = beta p + (1-beta) q: one
+// v_log of the mixture, clamped below at 2^-150 -- v_log reads a denormal or zero m as 0 (-inf), and
+// there p and q are < 2^-126 / min(beta, 1-beta), so what the clamped element adds is below 1e-35.
+//   pass A (sums in base 2, x ln 2 at the end)      pass B (c = kd coefficient, natural units)
+//   FKL  D  = sum p (lp - lq)                        g = c (q - p)
+//   RKL  D  = sum q (lq - lp)                        g = c ln2 q ((lq - lp) - D)
+//   JSD  D  = sum beta p (lp - lm) + (1-beta) q (lq - lm),  K = sum q (lq - lm)
+//                                                    g = c (1-beta) ln2 q ((lq - lm) - K)
+// plus the CE's cec (p1 - onehot), p1 = q when T = 1; the one-hot element is rewritten after pass B by
+// the lane that owns it, as in k_loss_grad_loca.  The row's term is stored already divided by the
+// row count R (rows, or n_valid from k_count_valid's coefs[0]: no host sync), so k_finalize sums
+// it with kl_scale = T^2; with KD_LOSS_ROWS_TARGETS the kd coefficient arrives without its 1/R
+// and a row outside the set skips pass A and writes zeros (its CE coefficient is 0 as well).
+struct DivRow {
+    float a, mp, cp, mq, cq, c1, c, cec, K, beta, omb;
+};
+
+template <int VARIANT, bool T1>
+__device__ __forceinline__ float div_grad(const DivRow& R, float t, float s) {
+    const float ds = s - R.mq, lq = fmaf(ds, R.a, -R.cq);
+    const float q = ex2(lq);
+    float g;
+    if (VARIANT == KD_LOSS_FKL) {
+        // K = c (+ cec at T = 1)
+        g = fmaf(q, R.K, -R.c * ex2(fmaf(t - R.mp, R.a, -R.cp)));
+    } else if (VARIANT == KD_LOSS_RKL) {
+        // c = kd ln2, K = -c D (+ cec at T = 1):  q (c (lq - lp) + K)
+        const float lp = fmaf(t - R.mp, R.a, -R.cp);
+        g = q * fmaf(lq - lp, R.c, R.K);
+    } else {
+        // c = kd (1-beta) ln2, K = -c K_row (+ cec at T = 1)
+        const float p = ex2(fmaf(t - R.mp, R.a, -R.cp));
+        const float lm = fmaxf(__builtin_amdgcn_logf(fmaf(R.omb, q, R.beta * p)), -150.f);
+        g = q * fmaf(lq - lm, R.c, R.K);
+    }
+    if (!T1) g = fmaf(ex2(fmaf(ds, KD_LOG2E, -R.c1)), R.cec, g);
+    return g;
+}
+
+template <int VARIANT, bool T1>
+__global__ void __launch_bounds__(LG_NT)
+k_loss_grad_div(const bf16* __restrict__ T_, int64_t ld_t, const bf16* __restrict__ S_, int64_t ld_s,
+                int V, int rows, float invT, float beta, int targets, const RowStats* __restrict__ stats,
+                const float* __restrict__ coefs, bf16* __restrict__ D_, int64_t ld_d,
+                float* __restrict__ part_kl) {
+    __shared__ float red[LG_NW];
+    const int tid = threadIdx.x;
+    // 1 / R and the kd coefficient (coefs: k_count_valid; both / the stored dlogits scale)
+    const float n_valid = coefs[0];
+    const float inv_r = targets ? (n_valid > 0.f ? 1.f / n_valid : 0.f) : 1.f / (float)rows;
+    const float ce_coef = coefs[1], kd_coef = targets ? coefs[2] * inv_r : coefs[2];
+    DivRow R;
+    R.a = invT * KD_LOG2E;
+    R.beta = beta;
+    R.omb = 1.f - beta;
+    for (int r = blockIdx.x; r < rows; r += gridDim.x) {
+        const RowStats st = stats[r];
+        bf16* drow = D_ != nullptr ? D_ + (int64_t)r * ld_d : nullptr;
+        if (targets && !st.valid) {   // outside the row set: no KD term, no KD gradient, no CE
+            if (tid == 0) part_kl[r] = 0.f;
+            if (drow != nullptr)
+                for (int v = tid * 8; v < V; v += LG_NT * 8) *(u32x4*)(drow + v) = u32x4{0u, 0u, 0u, 0u};
+            continue;
+        }
+        const bf16* srow = S_ + (int64_t)r * ld_s;
+        const bf16* trow = T_ + (int64_t)r * ld_t;
+        R.mp = st.mt; R.cp = log2f(st.zt);
+        R.mq = st.ms; R.cq = log2f(st.zs);
+        // ---- pass A: D (and JSD's K)
+        float term = 0.f, kacc = 0.f;
+        for (int v0 = tid * 8; v0 < V; v0 += LG_NT * 8 * LG_U) {
+            bf16x8 xtu[LG_U], xsu[LG_U];
+#pragma unroll
+            for (int u = 0; u < LG_U; ++u) {
+                const int v = v0 + u * LG_NT * 8;
+                if (v < V) { xtu[u] = *(const bf16x8*)(trow + v); xsu[u] = *(const bf16x8*)(srow + v); }
+            }
+#pragma unroll
+            for (int u = 0; u < LG_U; ++u) {
+                if (v0 + u * LG_NT * 8 >= V) break;
+                float t[8], sv[8];
+                bf16x8_to_f32(xtu[u], t);
+                bf16x8_to_f32(xsu[u], sv);
+#pragma unroll
+                for (int j = 0; j < 8; ++j) {
+                    const float lp = fmaf(t[j] - R.mp, R.a, -R.cp), lq = fmaf(sv[j] - R.mq, R.a, -R.cq);
+                    if (VARIANT == KD_LOSS_FKL) {
+                        term = fmaf(ex2(lp), lp - lq, term);
+                    } else if (VARIANT == KD_LOSS_RKL) {
+                        term = fmaf(ex2(lq), lq - lp, term);
+                    } else {
+                        const float q = ex2(lq), bp = R.beta * ex2(lp);
+                        const float lm = fmaxf(__builtin_amdgcn_logf(fmaf(R.omb, q, bp)), -150.f);
+                        const float dq = lq - lm;
+                        term = fmaf(bp, lp - lm, term);
+                        kacc = fmaf(q, dq, kacc);
+                    }
+                }
+            }
+        }
+        term = block_sum<LG_NW>(term, red);
+        if (VARIANT == KD_LOSS_JSD) {
+            kacc = block_sum<LG_NW>(kacc, red);
+            term = fmaf(R.omb, kacc, term);
+        }
+        if (tid == 0) part_kl[r] = term * KD_LN2 * inv_r;
+        if (drow == nullptr) continue;
+        // ---- pass B: dlogits
+        R.cec = st.valid ? ce_coef : 0.f;
+        R.c1 = log2f(st.zs1);
+        if (VARIANT == KD_LOSS_FKL) { R.c = kd_coef; R.K = kd_coef; }
+        else if (VARIANT == KD_LOSS_RKL) { R.c = kd_coef * KD_LN2; R.K = -R.c * term; }
+        else { R.c = kd_coef * R.omb * KD_LN2; R.K = -R.c * kacc; }
+        if (T1) R.K += R.cec;
+        for (int v0 = tid * 8; v0 < V; v0 += LG_NT * 8 * LG_U) {
+            bf16x8 xtu[LG_U], xsu[LG_U];
+#pragma unroll
+            for (int u = 0; u < LG_U; ++u) {
+                const int v = v0 + u * LG_NT * 8;
+                if (v < V) { xsu[u] = *(const bf16x8*)(srow + v); xtu[u] = *(const bf16x8*)(trow + v); }
+            }
+#pragma unroll
+            for (int u = 0; u < LG_U; ++u) {
+                const int v = v0 + u * LG_NT * 8;
+                if (v >= V) break;
+                float t[8], sv[8];
+                bf16x8_to_f32(xtu[u], t);
+                bf16x8_to_f32(xsu[u], sv);
+                bf16x8 out;
+#pragma unroll
+                for (int j = 0; j < 8; ++j) out[j] = (bf16)div_grad<VARIANT, T1>(R, t[j], sv[j]);
+                *(bf16x8*)(drow + v) = out;
+            }
+        }
+        // the CE one-hot: the lane that wrote labn's chunk rewrites that element (program order makes
+        // its second store land after the first)
+        const int labn = st.lab_next;
+        if (st.valid && ((labn >> 3) & (LG_NT - 1)) == tid) {
+            const float g = div_grad<VARIANT, T1>(R, (float)trow[labn], (float)srow[labn]);
+            drow[labn] = (bf16)(g - R.cec);
+        }
+    }
+}
+
 // LDS override-image slots of k_loss_grad_loca_rr<., rc> (64 B each): what leaves two (rc = 5) or three
 // (rc = 3) workgroups per CU their share of the 160 KB beside the kernel's static arrays
 inline int rr_ov_cap(int rc) { return rc >= 5 ? 1152 : 704; }
@@ -1190,8 +1345,13 @@ int launch_kd_loss(const void* teacher, int64_t ld_t, int V_t, const void* stude
                    int V_s, const int64_t* labels, int B, int L, kd_loss_params p, float* loss_out,
                    void* dlogits, int64_t ld_d, void* ws, size_t ws_bytes, void* stream_) {
     hipStream_t stream = as_stream(stream_);
-    const int variant = p.variant;
-    KD_CHECK_ARG(variant >= KD_LOSS_NONE && variant <= KD_LOSS_KL_LOGTARGET, "kd_loss: bad variant");
+    const int variant = p.variant & 0xff;
+    const bool div = variant >= KD_LOSS_FKL;   // the token-level divergences (k_loss_grad_div)
+    const bool targets = (p.variant & KD_LOSS_ROWS_TARGETS) != 0;
+    KD_CHECK_ARG(variant >= KD_LOSS_NONE && variant <= KD_LOSS_JSD && (p.variant & ~(0xff | KD_LOSS_ROWS_TARGETS)) == 0,
+                 "kd_loss: bad variant");
+    KD_CHECK_ARG(div || !targets, "kd_loss: KD_LOSS_ROWS_TARGETS needs KD_LOSS_FKL / RKL / JSD");
+    KD_CHECK_ARG(variant != KD_LOSS_JSD || (p.alpha > 0.f && p.alpha < 1.f), "kd_loss: JSD beta must be in (0, 1)");
     KD_CHECK_ARG(student && labels && loss_out && ws, "kd_loss: null pointer");
     KD_CHECK_ARG(variant == KD_LOSS_NONE || teacher, "kd_loss: teacher logits required");
     KD_CHECK_SHAPE(B > 0 && L > 0 && V_s > 0, "kd_loss: empty shape");
@@ -1262,7 +1422,9 @@ int launch_kd_loss(const void* teacher, int64_t ld_t, int V_t, const void* stude
     }
     const double N = (double)rows * (double)V_s;
     const float T = p.temperature;
-    const float kd_coef = (float)((double)p.kd_weight * T / N * p.grad_scale);
+    // the divergences are a mean over rows (N = rows); with KD_LOSS_ROWS_TARGETS over the n_valid target
+    // rows, a count only the device has: k_loss_grad_div applies that 1 / n_valid (N = 1 here)
+    const float kd_coef = (float)((double)p.kd_weight * T / (!div ? N : targets ? 1.0 : (double)rows) * p.grad_scale);
     const float ce_num = p.ce_weight * p.grad_scale;
     hipLaunchKernelGGL(k_count_valid, dim3(1), dim3(NT), 0, stream, labels, B, L, V_s, ce_num,
                        variant == KD_LOSS_NONE ? 0.f : kd_coef, p.dscale, p.dscale_given ? 1 : 0, coefs);
@@ -1303,6 +1465,20 @@ int launch_kd_loss(const void* teacher, int64_t ld_t, int V_t, const void* stude
     } else if (loca_fast) {
         hipLaunchKernelGGL(k_loss_grad_loca<false>, dim3(lg_grid), dim3(LG_NT), smem, stream, T_, ld_t, S_, ld_s, V_s,
                            rows, invT, p.clamp_min, stats, ovr, mask, coefs, D_, ld_d, part_kl);
+    } else if (div) {
+#define KD_LAUNCH_DIV(VAR)                                                                                  \
+    do {                                                                                                    \
+        if (invT == 1.f)                                                                                    \
+            hipLaunchKernelGGL((k_loss_grad_div<VAR, true>), dim3(lg_grid), dim3(LG_NT), 0, stream, T_, ld_t, S_, ld_s, \
+                               V_s, rows, invT, p.alpha, targets ? 1 : 0, stats, coefs, D_, ld_d, part_kl);  \
+        else                                                                                                \
+            hipLaunchKernelGGL((k_loss_grad_div<VAR, false>), dim3(lg_grid), dim3(LG_NT), 0, stream, T_, ld_t, S_, ld_s, \
+                               V_s, rows, invT, p.alpha, targets ? 1 : 0, stats, coefs, D_, ld_d, part_kl);  \
+    } while (0)
+        if (variant == KD_LOSS_FKL) KD_LAUNCH_DIV(KD_LOSS_FKL);
+        else if (variant == KD_LOSS_RKL) KD_LAUNCH_DIV(KD_LOSS_RKL);
+        else KD_LAUNCH_DIV(KD_LOSS_JSD);
+#undef KD_LAUNCH_DIV
     } else switch (variant) {
         case KD_LOSS_NONE: KD_LAUNCH_LG(KD_LOSS_NONE); break;
         case KD_LOSS_LOCA: KD_LAUNCH_LG(KD_LOSS_LOCA); break;
@@ -1311,7 +1487,8 @@ int launch_kd_loss(const void* teacher, int64_t ld_t, int V_t, const void* stude
     }
 #undef KD_LAUNCH_LG
     KD_LAUNCH_CHECK("k_loss_grad");
-    const double kl_scale = (variant == KD_LOSS_NONE) ? 0.0 : (double)T * T / N;
+    // (k_loss_grad_div's row terms are already divided by the row count)
+    const double kl_scale = (variant == KD_LOSS_NONE) ? 0.0 : div ? (double)T * T : (double)T * T / N;
     hipLaunchKernelGGL(k_finalize, dim3(1), dim3(NT), 0, stream, stats, part_kl, rows, kl_scale,
                        p.kd_weight, p.ce_weight, p.out_scale, p.out_accumulate ? 1 : 0, loss_out);
     KD_LAUNCH_CHECK("k_finalize");

@@ -245,8 +245,24 @@ class _KDBase(_Base):
     def __init__(self, model_name_student, model_name_teacher, processor=None, learning_rate=1e-5, phase=1,
                  seed_teacher: int = 1, seed_student: int = 2, state_dict=None, loss_group_size: int | None = None,
                  accumulate_grad_batches: int | None = None, teacher_fp8: bool | str = False,
-                 grad_comm_dtype=None, teacher_residual_f32: bool = False, **_ignored):
+                 grad_comm_dtype=None, teacher_residual_f32: bool = False, divergence: str | None = None,
+                 divergence_beta: float = 0.5, kd_rows: str = "all", **_ignored):
         super().__init__()
+        # divergence: the teacher logit term of _loss_spec() replaced by a token-level forward KL
+        # ("fkl"), reverse KL ("rkl") or generalized JSD ("jsd", divergence_beta the weight on the
+        # teacher); T and the weights stay the module's.  kd_rows "targets": that term over the
+        # positions the CE trains on only.  None: the reference's objective, launch for launch.
+        # Checked before any device work.
+        if divergence is None:
+            if kd_rows != "all":
+                raise ValueError(f"kd_rows={kd_rows!r} needs a divergence ('fkl', 'rkl' or 'jsd')")
+        else:
+            if divergence not in ops.DIVERGENCES:
+                raise ValueError(f"divergence {divergence!r}: expected None or one of {ops.DIVERGENCES}")
+            if not self.uses_teacher:
+                raise ValueError(f"{type(self).__name__} has no teacher: no logit term for divergence={divergence!r}")
+            ops.check_divergence_args(divergence, divergence_beta, kd_rows)
+        self.divergence, self.divergence_beta, self.kd_rows = divergence, float(divergence_beta), kd_rows
         self.phase = phase
         self.learning_rate = learning_rate
         self.processor = processor
@@ -406,6 +422,10 @@ class _KDBase(_Base):
     def forward(self, batch, train: bool = False):
         """The reference's forward(batch) (DT:206-271): total loss as a 0-d fp32 tensor."""
         variant, T, kd_w, ce_w, ctr_w = self._loss_spec()
+        div_kw = {}
+        if self.divergence is not None:
+            variant = self.divergence
+            div_kw = {"beta": self.divergence_beta, "rows": self.kd_rows}
         labels = batch["labels"]
         image_sizes = batch["image_sizes"]
         B, L = batch["depth_input_ids"].shape
@@ -470,7 +490,7 @@ class _KDBase(_Base):
                                 row_base=g * G * L, dscale=dscale, dscale_given=g > 0,
                                 s_row_stats=None if s_rst is None else s_rst[rs],
                                 t_row_stats=None if (s_rst is None or t_rst is None) else t_rst[rs],
-                                s_stats=None if s_st is None else s_st[rs], standin_count=self.loss_standins)
+                                s_stats=None if s_st is None else s_st[rs], standin_count=self.loss_standins, **div_kw)
         del s_rst, t_rst, s_st
         if self.keep_logits:
             self.last_logits = (s3, t3)
@@ -658,7 +678,8 @@ class _KDBase(_Base):
     def _run_hparams(self):
         return {"loss_group_size": self.loss_group_size, "accumulate_grad_batches": self.accumulate_grad_batches,
                 "teacher_fp8": getattr(self, "teacher_fp8", False),
-                "teacher_residual_f32": getattr(self, "teacher_residual_f32", False)}
+                "teacher_residual_f32": getattr(self, "teacher_residual_f32", False),
+                "divergence": self.divergence, "divergence_beta": self.divergence_beta, "kd_rows": self.kd_rows}
 
     def on_train_epoch_end(self):
         """A batch rejected among the last steps of an epoch is reported here (the reference
@@ -696,7 +717,8 @@ class _KDBase(_Base):
             elif name in hp:
                 args[name] = hp[name]
         if var_kw:   # the saved run knobs a subclass forwards to _KDBase through **kw
-            for name in ("loss_group_size", "accumulate_grad_batches", "teacher_fp8", "teacher_residual_f32"):
+            for name in ("loss_group_size", "accumulate_grad_batches", "teacher_fp8", "teacher_residual_f32",
+                         "divergence", "divergence_beta", "kd_rows"):
                 if name in hp and name not in args and name not in kw:
                     args[name] = hp[name]
         kw.pop("torch_dtype", None)   # the build's weights are bf16 in HBM whatever the caller's dtype

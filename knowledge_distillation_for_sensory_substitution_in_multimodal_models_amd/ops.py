@@ -125,7 +125,20 @@ def kd_loss_student_stats(student_logits: torch.Tensor, temperature: float = 1.0
 
 
 VARIANTS = {"none": NV.KD_LOSS_NONE, "loca": NV.KD_LOSS_LOCA, "kl": NV.KD_LOSS_KL,
-            "kl_logtarget": NV.KD_LOSS_KL_LOGTARGET}
+            "kl_logtarget": NV.KD_LOSS_KL_LOGTARGET,
+            "fkl": NV.KD_LOSS_FKL, "rkl": NV.KD_LOSS_RKL, "jsd": NV.KD_LOSS_JSD}
+DIVERGENCES = ("fkl", "rkl", "jsd")   # token-level: sum over V, mean over the row set
+ROW_SETS = ("all", "targets")
+
+
+def check_divergence_args(variant: str, beta: float, rows: str):
+    """The ValueErrors of the divergence keywords (before any device work)."""
+    if rows not in ROW_SETS:
+        raise ValueError(f"rows {rows!r}: expected 'all' or 'targets'")
+    if rows != "all" and variant not in DIVERGENCES:
+        raise ValueError(f"rows={rows!r} needs one of the variants {DIVERGENCES}, not {variant!r}")
+    if variant == "jsd" and not 0.0 < float(beta) < 1.0:
+        raise ValueError(f"beta {beta!r}: the JSD mixture weight must lie in (0, 1)")
 
 
 def kd_loss_fwd_bwd(student_logits: torch.Tensor, teacher_logits: torch.Tensor | None,
@@ -138,7 +151,7 @@ def kd_loss_fwd_bwd(student_logits: torch.Tensor, teacher_logits: torch.Tensor |
                     dscale: torch.Tensor | None = None, dscale_given: bool = False,
                     s_row_stats: torch.Tensor | None = None, t_row_stats: torch.Tensor | None = None,
                     s_stats: torch.Tensor | None = None, loca_path: str = "auto", rr_poll_us: int | None = None,
-                    standin_count: torch.Tensor | None = None):
+                    standin_count: torch.Tensor | None = None, beta: float = 0.5, rows: str = "all"):
     """Fused KD-loss forward + backward (include/kdstep.h kd_loss_fwd_bwd).
 
     student_logits [B, L, V_s] bf16 (last dim contiguous), teacher_logits [B, L, V_t] bf16,
@@ -160,7 +173,13 @@ def kd_loss_fwd_bwd(student_logits: torch.Tensor, teacher_logits: torch.Tensor |
     rr_poll_us: the register-resident kernel's partner poll budget (None = 200 us; 0 = every partner
     partial recomputed by the waiting slice); standin_count (device int32 [1]) += the partials that
     were recomputed (kd_loss_params.loca_path / rr_poll_us_p1 / standin_count).
+
+    variant "fkl" / "rkl" / "jsd": the token-level forward KL, reverse KL and generalized JSD(beta)
+    (kdstep.h KD_LOSS_FKL / RKL / JSD: a sum over the vocabulary, a mean over rows); beta is JSD's
+    weight on the teacher, 0 < beta < 1.  rows "all" takes that mean over every position, "targets"
+    over the positions whose shifted label is a CE target (these three variants only).
     """
+    check_divergence_args(variant, beta, rows)
     B, L, V_s = student_logits.shape
     _require(student_logits, torch.bfloat16, "student_logits")
     _require(labels, torch.int64, "labels")
@@ -168,6 +187,10 @@ def kd_loss_fwd_bwd(student_logits: torch.Tensor, teacher_logits: torch.Tensor |
         raise RuntimeError("student_logits: rows must be uniformly strided with a contiguous last dim")
     labels = labels.contiguous()
     v = VARIANTS[variant]
+    if variant == "jsd":
+        alpha = beta   # kd_loss_params.alpha carries JSD's mixture weight
+    if rows == "targets":
+        v |= NV.KD_LOSS_ROWS_TARGETS
     if teacher_logits is not None:
         _require(teacher_logits, torch.bfloat16, "teacher_logits")
         if teacher_logits.stride(2) != 1 or teacher_logits.stride(0) != L * teacher_logits.stride(1):
